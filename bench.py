@@ -13,9 +13,18 @@ raster Mpix/s from a separate timed loop of full forwards).  Before the W warm-u
 untimed CG calls run for ~200 ms so the GPU clocks are at the steady state of a running solve
 (reported as "clock_settle"; the first call after the host-side setup runs ~15% slower).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     torchrun --nproc-per-node N bench.py --gpus N ...
 Prints ONE JSON line on rank 0.
+
+A plain run does what the headline needs and nothing else: scene setup, clock settle, the W warm-up and K timed CG
+iterations, then the line with the headline fields (`value`, `ms_per_step`, ...).  `--dump-outputs DIR` also writes
+what the timed call returned -- the CG iterate x after its K iterations -- as DIR/x.npy (float32; a fixed seeded
+sample of its elements when the vector is larger than the dump's budget).  The scene is seeded, so two builds run with
+the same arguments see the same inputs and their dumps compare element for element.  Every other measurement (the
+loop with the stopping tests, the full SH-rest layout, raster Mpix/s, stage times and rooflines, the LM steps, the
+drop-in paths, SSIM, first-order, memory slices, the CPU baseline) runs under `--full`, which adds its fields to the
+same line; `--no-side`, `--no-cpu-baseline` and `--no-rank-slices` trim a `--full` run.
 """
 import argparse
 import ctypes
@@ -55,7 +64,15 @@ def parse():
     ap.add_argument("--no-side", action="store_true", help="headline + roofline only (profiling runs)")
     ap.add_argument("--no-rank-slices", action="store_true",
                     help="skip the per-rank memory / time slices of configs[3] and configs[4] (N = 1 only)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other measurement (raster, rooflines, LM steps, drop-in paths, "
+                         "memory, CPU baseline) and add its fields to the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed call returned (the CG iterate x) as DIR/x.npy")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def spawn_ranks(args):
@@ -104,6 +121,7 @@ def main():
     args = parse()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args))
+    side = args.full and not args.no_side  # the side measurements (and the validation views they need)
     # stdout carries exactly the one JSON line: everything else written to fd 1 -- RCCL prints its version banner
     # there at communicator setup -- goes to stderr
     sys.stdout.flush()
@@ -163,7 +181,7 @@ def main():
     del gt_prob
     # the line search's validation views (train_jvp.py:214-216: 50 cameras), GT from the same perturbed model; each
     # rank renders the GT of the views its LossEvaluator will hold (lm_step shards them with shard_views)
-    val_all = orbit_cameras(args.val_views, W, H, seed=5) if not args.no_side else []
+    val_all = orbit_cameras(args.val_views, W, H, seed=5) if side else []
     mine_val = shard_views(len(val_all), rank, world_size)
     for c0 in range(0, len(mine_val), 8):
         chunk = [val_all[i].to(device) for i in mine_val[c0:c0 + 8]]
@@ -229,6 +247,50 @@ def main():
     barrier()
     t_cg = max_over_ranks(time.perf_counter() - t0)
     ms_per_step = 1e3 * t_cg / args.steps
+
+    headline = {
+        "metric": METRIC,
+        "value": n_views * args.steps / t_cg,
+        "unit": "view-matvec/s (one (J^T J + D) application per 1080p view, 1M Gaussians)",
+        "n_gpus": world_size, "ranks": dist.get_world_size() if world_size > 1 else 1,
+        "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic (seeded Gaussians / orbit cameras / GT = render of perturbed model)",
+        "config": {"workload": f"LM CG iteration, {args.P} Gaussians SH{args.sh}, {args.views_per_gpu}x{W}x{H} "
+                               f"view(s) per GPU (BASELINE configs[2]; configs[3] at 8 GPUs)",
+                   "P": args.P, "sh_degree": args.sh, "width": W, "height": H,
+                   "views_total": n_views, "parallelism": f"views sharded x{world_size}",
+                   "exchange": prob.exchange if (world_size > 1 or forced) else "none",
+                   "sh_rest_projected": bool(prob.layout.rest_projected)},
+        "cg_matvecs_per_s": args.steps / t_cg,
+        "clock_settle": dict(settle, note="untimed CG calls before the warm-up and timed steps: the GPU clocks "
+                                          "at their steady state, as in a running LM solve"),
+        "num_rendered": n_rendered,
+    }
+
+    def finish(line):
+        if rank == 0:
+            json_out.write(json.dumps(line) + "\n")
+            json_out.flush()
+        if dist.is_initialized():
+            dist.barrier()
+            from gslm.parallel import close_native_comms
+            close_native_comms()  # (GSLM_COMM=native) every rank at the same point, before the process group goes
+            dist.destroy_process_group()
+
+    if args.dump_outputs:
+        # x of the timed call, whole (a Gaussian-sharded operator holds a shard per rank: gathered, every rank calls)
+        x_out = prob.gather_full(x) if getattr(prob, "exchange", None) == "gaussian" else x
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"x": x_out})
+        del x_out
+    if not args.full:
+        finish(headline)
+        return
 
     # the same K iterations with the reference's stopping tests each iteration (conjugate_gradient.py:88-117: delta,
     # the residual monitor b^2 - <x, g> - <x, s>, the gamma tolerance), evaluated on the device (gslm_cg_monitor; the
@@ -405,8 +467,6 @@ def main():
     # the side measurements below run on one view and need the memory of the batch's problem back
     # (at configs[4], 5M Gaussians x 32 4K views, that is ~100 GB)
     n_views_local = len(loc.views)
-    sh_proj = prob.layout.rest_projected
-    exchange = prob.exchange if (world_size > 1 or forced) else "none"
     view0 = prob.views[0].view if prob.views else None
     del prob, loc, vr, vs, ys, x, xv, g
     torch.cuda.empty_cache()
@@ -414,7 +474,7 @@ def main():
     raster_streams = None
 
     fb = c0_gpu = lm = lm_tv = lm_ref = ssim = fo = dropin = None
-    if not args.no_side:
+    if side:
         # ---------------- BASELINE configs[2] / [3] as train_jvp.py runs it, on every rank: one full LM step (loss,
         # J^T b, CGLS with 10 iterations and the reference's stopping tests, the 7-point line search on the
         # reference's 50 validation views), sharded over the ranks; and with the training batch as the validation set
@@ -454,7 +514,7 @@ def main():
 
     # ---------------- what one rank of the 8-GPU configs holds, emulated on this GPU (N = 1 only)
     rank_slices = None
-    if world_size == 1 and not forced and not args.no_side and not args.no_rank_slices:
+    if world_size == 1 and not forced and side and not args.no_rank_slices:
         rank_slices = rank_slice_memory(model, cams_all, val_all, bg, device)
 
     # ---------------- the raster forwards with RASTER_STREAMS renders in flight on as many HIP streams (independent
@@ -463,7 +523,7 @@ def main():
     # burst of 8-stream work the process's later kernels run slower (the stage timing measured k_render_matvec 7% over
     # rocprof's solo average; the LM step 96.3 ms against 91-92 in tools/exp/lm_phases.py on the same box, every
     # phase 6-10% slower, profiles/r06/ab_bench_order/), which an LM run that never issues such a burst does not see
-    if not args.no_side and view0 is not None:
+    if side and view0 is not None:
         from gslm.lm import ViewRaster
         S = RASTER_STREAMS
         rasters = [ViewRaster(view0, device) for _ in range(S)]
@@ -494,7 +554,7 @@ def main():
 
     # ---------------- CPU baseline (rank 0, N = 1 only): the oracle on host cores, bounded sample
     cpu = None
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline and not args.no_side:
+    if rank == 0 and world_size == 1 and not args.no_cpu_baseline and side:
         from oracle.cpu_baseline import cpu_matvec_rate
         cm = synthetic_gaussians(args.P, args.sh, seed=0, s0=args.s0, device="cpu")
         cc = orbit_cameras(1, W, H, seed=1)[0]
@@ -519,35 +579,17 @@ def main():
                "configs0": dict(c0, config="BASELINE configs[0]: 2000 Gaussians SH0, one 256x256 view, oracle "
                                            "forward / JVP / VJP, 1 warm-up + median of 5, no extrapolation")}
 
+    line = None
     if rank == 0:
-        line = {
-            "metric": METRIC,
-            "value": n_views * args.steps / t_cg,
-            "unit": "view-matvec/s (one (J^T J + D) application per 1080p view, 1M Gaussians)",
-            "n_gpus": world_size, "ranks": dist.get_world_size() if world_size > 1 else 1,
-            "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f32",
-            "data": "synthetic (seeded Gaussians / orbit cameras / GT = render of perturbed model)",
-            "config": {"workload": f"LM CG iteration, {args.P} Gaussians SH{args.sh}, {args.views_per_gpu}x{W}x{H} "
-                                   f"view(s) per GPU (BASELINE configs[2]; configs[3] at 8 GPUs)",
-                       "P": args.P, "sh_degree": args.sh, "width": W, "height": H,
-                       "views_total": n_views, "parallelism": f"views sharded x{world_size}",
-                       "exchange": exchange, "sh_rest_projected": bool(sh_proj)},
-            "cg_matvecs_per_s": args.steps / t_cg,
+        line = dict(headline)
+        line.update({
             "cg_checked": cg_checked,
-            "clock_settle": dict(settle, note="untimed CG calls before the warm-up and timed steps: the GPU clocks "
-                                              "at their steady state, as in a running LM solve"),
             "raster_mpix_s": mpix,
             "forward_ms_per_view": 1e3 * t_fwd / fsteps / max(n_views_local, 1),
             "raster_sync": {"mpix_s": mpix_sync, "forward_ms_per_view": 1e3 * t_fwd_sync / fsteps / max(n_views_local, 1),
                             "note": "the same forwards with the pair count read back by the host before the binning "
                                     "(gslm_forward's protocol, as the upstream forward)"},
             "raster_streams": raster_streams,
-            "num_rendered": n_rendered,
             "stage_ms": {"tangent_preprocess": tangent_ms, "render_matvec": render_ms, "gather_backward": gather_ms},
             "roofline": {"bound": "hbm", "kernel": "k_render_matvec", "achieved": achieved, "peak": HBM_PEAK_GBS,
                          "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
@@ -574,14 +616,28 @@ def main():
             "first_order": fo,
             "cg_full_layout": cg_full,
             "peak_mem": dict(peak_mem, rank_slices=rank_slices),
-        }
-        json_out.write(json.dumps(line) + "\n")
-        json_out.flush()
-    if dist.is_initialized():
-        dist.barrier()
-        from gslm.parallel import close_native_comms
-        close_native_comms()  # (GSLM_COMM=native) every rank at the same point, before the process group goes
-        dist.destroy_process_group()
+        })
+    finish(line)
+
+
+MAX_DUMP_ELEMS = 8 << 20  # float32 elements per dumped array (32 MB)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: each array as out_dir/<name>.npy, float32.  An array of more than MAX_DUMP_ELEMS elements is
+    sampled: one element from every stride-long run of the flat array, its offset in the run drawn from a generator
+    seeded with 0 -- the same elements for every run with the same arguments."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in arrays.items():
+        flat = t.detach().reshape(-1)
+        n = flat.numel()
+        if n > MAX_DUMP_ELEMS:
+            stride = -(-n // MAX_DUMP_ELEMS)
+            base = torch.arange(0, n - stride + 1, stride, dtype=torch.int64)
+            idx = base + torch.randint(0, stride, base.shape, generator=torch.Generator().manual_seed(0))
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), flat.to(torch.float32).cpu().numpy())
 
 
 def rank_slice_memory(model, cams_all, val_all, bg, device):

@@ -13,7 +13,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 ROOT=$(pwd)
-PROFARGS="--no-cpu-baseline --steps 10 --warmup 3 --forward-steps 8 $*"
+PROFARGS="--full --no-cpu-baseline --steps 10 --warmup 3 --forward-steps 8 $*"
 # the headline and the forward alone (no side measurements: one stream, no line-search overlap in the kernel averages)
 SOLOARGS="$PROFARGS --no-side"
 
@@ -24,7 +24,7 @@ step_tests() {
 }
 
 step_tests \
-&& timeout -k 10 600 python bench.py "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" \
+&& timeout -k 10 600 python bench.py --full "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" \
 && (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d "$ROOT/$OUT/stats" -o run \
       -- python3 "$ROOT/bench.py" $PROFARGS > "$ROOT/$OUT/prof_bench.json" 2> "$ROOT/$OUT/prof.err") \
 && (cd /tmp && timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d "$ROOT/$OUT/stats_solo" -o run \

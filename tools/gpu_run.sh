@@ -11,6 +11,7 @@ if [ "${TESTS:-}" != "none" ]; then
   tail -3 gpurun_out/$TAG/gpu_tests.log
 fi
 if [ "${BENCH:-1}" = "1" ]; then
+  BENCH_ARGS=${BENCH_ARGS:---full --steps 20 --warmup 5}  # the whole line, as the stored bench.json files hold it
   timeout -k 10 ${BENCH_TIMEOUT:-600} python -u bench.py ${BENCH_ARGS:---steps 20 --warmup 5} > gpurun_out/$TAG/bench.json 2> gpurun_out/$TAG/bench.err \
     || { echo "bench failed: $?"; tail -30 gpurun_out/$TAG/bench.err; exit 1; }
   cat gpurun_out/$TAG/bench.json

@@ -9,7 +9,7 @@ OUT=gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 ROOT=$(pwd)
-PROG="$ROOT/bench.py --no-cpu-baseline --no-side --steps 3 --warmup 1 --forward-steps 2"
+PROG="$ROOT/bench.py --full --no-cpu-baseline --no-side --steps 3 --warmup 1 --forward-steps 2"
 [ "${3:-bench}" = "union" ] && PROG="$ROOT/tools/exp/union_kernels.py --reps 3"
 run() {  # $1 = pass name, rest = counters
   local name=$1; shift
