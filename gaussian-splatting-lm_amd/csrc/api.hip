@@ -734,10 +734,13 @@ static int build_xpby(const gslm_matvec_opts* opts, const gslm_grads* vin, int R
   return GSLM_OK;
 }
 
-int gslm_matvec_view_ex(const gslm_view* view, const gslm_gaussians* gi, const gslm_grads* vin,
-                        const float* pixel_weight, int32_t mask_xyz, const void* geom, const void* binning,
-                        int64_t N, const void* image, void* scratch, size_t scratch_bytes, const gslm_grads* y,
-                        const gslm_matvec_opts* opts, void* stream) {
+// gslm_matvec_view_ex (na < 0) and gslm_matvec_view_active (na >= 0: the groups of vin, y and the fused direction
+// update hold the na Gaussians ids[0 .. na) only)
+static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gslm_grads* vin,
+                       const float* pixel_weight, int32_t mask_xyz, const void* geom, const void* binning,
+                       int64_t N, const void* image, void* scratch, size_t scratch_bytes, const gslm_grads* y,
+                       const gslm_matvec_opts* opts, const int32_t* ids, int64_t na, const uint32_t* hrow,
+                       void* stream) {
   DebugScope dbg_scope(view != nullptr && view->debug != 0, stream);
   Bound b;
   int st = bind_all(view, gi, geom, binning, N, image, scratch, scratch_bytes, &b);
@@ -746,7 +749,20 @@ int gslm_matvec_view_ex(const gslm_view* view, const gslm_gaussians* gi, const g
   const int32_t stages = (opts && opts->stages) ? opts->stages : GSLM_STAGE_ALL;
   const double* damp7 = opts ? opts->damp7 : nullptr;
   double* dot_out = opts ? opts->dot_vy : nullptr;
-  if (dot_out && (!opts->dot_scratch || opts->dot_scratch_bytes < gslm_dot_scratch_bytes(b.g.P))) {
+  const bool active = na >= 0;
+  const int64_t rows = active ? na : b.g.P;  // rows of every group of vin and y
+  if (active) {
+    if (na > b.g.P || (na > 0 && (!ids || !hrow))) {
+      set_error("matvec_view_active: 0 <= n_active <= P, a non-NULL list and its row offsets");
+      return GSLM_ERR_INVALID;
+    }
+    if (!mask_xyz || !opts || !(opts->flags & GSLM_MV_TAIL_CLEAN) || (stages & GSLM_STAGE_SCREEN) || opts->trec_in) {
+      set_error("matvec_view_active: needs mask_xyz and GSLM_MV_TAIL_CLEAN (the list comes from that row map); "
+                "no SCREEN stage, no trec_in");
+      return GSLM_ERR_INVALID;
+    }
+  }
+  if (dot_out && (!opts->dot_scratch || opts->dot_scratch_bytes < gslm_dot_scratch_bytes(rows))) {
     set_error("matvec: dot scratch too small");
     return GSLM_ERR_CAPACITY;
   }
@@ -792,7 +808,8 @@ int gslm_matvec_view_ex(const gslm_view* view, const gslm_gaussians* gi, const g
     return GSLM_ERR_INVALID;
   }
   if ((stages & GSLM_STAGE_TANGENT) &&
-      (st = launch_tangent_pre(b.v, b.g, t, nullptr, b.gb, b.sb, fused_xpby ? &xp : nullptr, s, mask_xyz != 0)))
+      (st = launch_tangent_pre(b.v, b.g, t, nullptr, b.gb, b.sb, fused_xpby ? &xp : nullptr, s, mask_xyz != 0, ids,
+                               na)))
     return st;
   float* jv_out = opts ? opts->jv_out : nullptr;
   if (jv_out) {
@@ -827,10 +844,83 @@ int gslm_matvec_view_ex(const gslm_view* view, const gslm_gaussians* gi, const g
   if (!(stages & GSLM_STAGE_GATHER)) return GSLM_OK;
   double* part = dot_out ? (double*)opts->dot_scratch : nullptr;
   if ((st = launch_gather_lm(b.v, b.g, b.gb, b.sb, make_gradk(y), make_gradk(vin), damp7,
-                             (stages & GSLM_STAGE_OVERWRITE) != 0, mask_xyz != 0, part, s, proj)))
+                             (stages & GSLM_STAGE_OVERWRITE) != 0, mask_xyz != 0, part, s, proj, ids, na, hrow)))
     return st;
-  if (dot_out) return gslm_dot_finalize(part, (int32_t)((b.g.P + 255) / 256), dot_out, stream);
+  if (dot_out) return gslm_dot_finalize(part, (int32_t)((rows + 255) / 256), dot_out, stream);
   return GSLM_OK;
+}
+
+int gslm_matvec_view_ex(const gslm_view* view, const gslm_gaussians* gi, const gslm_grads* vin,
+                        const float* pixel_weight, int32_t mask_xyz, const void* geom, const void* binning,
+                        int64_t N, const void* image, void* scratch, size_t scratch_bytes, const gslm_grads* y,
+                        const gslm_matvec_opts* opts, void* stream) {
+  return matvec_view(view, gi, vin, pixel_weight, mask_xyz, geom, binning, N, image, scratch, scratch_bytes, y, opts,
+                     nullptr, -1, nullptr, stream);
+}
+
+int gslm_matvec_view_active(const gslm_view* view, const gslm_gaussians* gi, const gslm_grads* vin,
+                            const float* pixel_weight, int32_t mask_xyz, const void* geom, const void* binning,
+                            int64_t N, const void* image, void* scratch, size_t scratch_bytes, const gslm_grads* y,
+                            const gslm_matvec_opts* opts, const int32_t* active_ids, const uint32_t* active_rows,
+                            int64_t n_active, void* stream) {
+  if (n_active < 0) { set_error("matvec_view_active: negative n_active"); return GSLM_ERR_INVALID; }
+  return matvec_view(view, gi, vin, pixel_weight, mask_xyz, geom, binning, N, image, scratch, scratch_bytes, y, opts,
+                     active_ids, n_active, active_rows, stream);
+}
+
+// the active list's workspace: the flags / their scan [P], the scan's block sums, its total
+static size_t active_work_layout(int64_t P, void* base, uint32_t** flags, uint32_t** tmp, uint32_t** total) {
+  Carver c{(char*)base};
+  uint32_t* f = c.take<uint32_t>(P > 0 ? P : 1);
+  uint32_t* t = c.take<uint32_t>(scan_tmp_bytes(P > 0 ? P : 1) / 4);
+  uint32_t* n = c.take<uint32_t>(4);
+  if (flags) { *flags = f; *tmp = t; *total = n; }
+  return c.off;
+}
+
+size_t gslm_active_list_bytes(int64_t P) { return active_work_layout(P, nullptr, nullptr, nullptr, nullptr); }
+
+int gslm_active_list(const void* geom, int64_t P, int64_t N, const void* scratch, size_t scratch_bytes, void* work,
+                     size_t work_bytes, int32_t* ids_dev, uint32_t* rows_dev, int64_t* count_dev, void* stream) {
+  if (P < 0 || N < 0 || !geom || !scratch || !work || !count_dev || !rows_dev || (P > 0 && !ids_dev)) {
+    set_error("active_list: NULL workspace / output or negative size");
+    return GSLM_ERR_INVALID;
+  }
+  if (scratch_bytes < gslm_scratch_bytes(P, N) || work_bytes < gslm_active_list_bytes(P)) {
+    set_error("active_list: scratch or work workspace too small");
+    return GSLM_ERR_CAPACITY;
+  }
+  GeomBufs gb;
+  ScratchBufs sb;
+  geom_layout(P, const_cast<void*>(geom), &gb);
+  scratch_layout(P, N, const_cast<void*>(scratch), &sb);
+  uint32_t *flags, *tmp, *total;
+  active_work_layout(P, work, &flags, &tmp, &total);
+  return launch_active_list(P, N, gb, sb, flags, tmp, total, ids_dev, rows_dev, count_dev, (hipStream_t)stream);
+}
+
+int gslm_inspect_rowmap(const void* geom, int64_t P, int64_t N, const void* scratch, size_t scratch_bytes,
+                        uint32_t* goff, uint32_t* hscan, void* stream) {
+  if (P < 0 || N < 0 || !geom || !scratch) { set_error("inspect_rowmap: NULL workspace or negative size"); return GSLM_ERR_INVALID; }
+  if (scratch_bytes < gslm_scratch_bytes(P, N)) { set_error("inspect_rowmap: scratch workspace too small"); return GSLM_ERR_CAPACITY; }
+  GeomBufs gb;
+  ScratchBufs sb;
+  geom_layout(P, const_cast<void*>(geom), &gb);
+  scratch_layout(P, N, const_cast<void*>(scratch), &sb);
+  hipStream_t s = (hipStream_t)stream;
+  if (goff && P > 0) GSLM_HIP_CHECK(hipMemcpyAsync(goff, gb.goff, (size_t)P * 4, hipMemcpyDeviceToDevice, s));
+  if (hscan) GSLM_HIP_CHECK(hipMemcpyAsync(hscan, sb.hscan, (size_t)(N + 1) * 4, hipMemcpyDeviceToDevice, s));
+  return GSLM_OK;
+}
+
+int gslm_active_pack(const float* src, float* dst, const int32_t* active_ids, int64_t n_active, int64_t P,
+                     const int32_t* widths, int32_t ngroups, int64_t tail_n, void* stream) {
+  return launch_active_pack(true, src, dst, active_ids, n_active, P, widths, ngroups, tail_n, (hipStream_t)stream);
+}
+
+int gslm_active_unpack(const float* src, float* dst, const int32_t* active_ids, int64_t n_active, int64_t P,
+                       const int32_t* widths, int32_t ngroups, int64_t tail_n, void* stream) {
+  return launch_active_pack(false, src, dst, active_ids, n_active, P, widths, ngroups, tail_n, (hipStream_t)stream);
 }
 
 int gslm_sh_rest_project(const gslm_view* view, const gslm_gaussians* gi, int32_t mode, const float* in,

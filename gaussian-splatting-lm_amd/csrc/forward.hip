@@ -639,6 +639,65 @@ int launch_lm_rowmap(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, cons
   return GSLM_OK;
 }
 
+// ---- the active list (gslm_active_list), once per geometry ----
+// Gaussian i is active when it owns at least one head row of the LM row map: hscan[goff + tiles] > hscan[goff].
+__device__ __forceinline__ uint32_t owns_head_row(int64_t i, const uint32_t* __restrict__ tiles,
+                                                  const uint32_t* __restrict__ goff,
+                                                  const uint32_t* __restrict__ hscan) {
+  const uint32_t n = tiles[i];
+  if (n == 0) return 0u;
+  const uint32_t o = goff[i];
+  return hscan[o + n] > hscan[o] ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(256) void k_active_flags(int64_t P, const uint32_t* __restrict__ tiles,
+                                                       const uint32_t* __restrict__ goff,
+                                                       const uint32_t* __restrict__ hscan, uint32_t* __restrict__ flags) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < P) flags[i] = owns_head_row(i, tiles, goff, hscan);
+}
+
+// pos = the exclusive scan of the flags: ids[pos[i]] = i for the active i (ascending), *count = their number, and
+// hrow[pos[i]] = the first head row of i, hrow[*count] = the number of head rows: the rows of list entry j are
+// [hrow[j], hrow[j + 1]) -- the Gaussians between two listed ones own none -- so the list's gather reads its row
+// offsets coalesced, without the goff -> hscan chain by id
+__global__ __launch_bounds__(256) void k_active_scatter(int64_t P, int64_t N, const uint32_t* __restrict__ tiles,
+                                                         const uint32_t* __restrict__ goff,
+                                                         const uint32_t* __restrict__ hscan,
+                                                         const uint32_t* __restrict__ pos,
+                                                         const uint32_t* __restrict__ total, int32_t* __restrict__ ids,
+                                                         uint32_t* __restrict__ hrow, int64_t* __restrict__ count) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i == 0) {
+    *count = (int64_t)*total;
+    hrow[*total] = hscan[N];
+  }
+  if (i < P && owns_head_row(i, tiles, goff, hscan)) {
+    ids[pos[i]] = (int32_t)i;
+    hrow[pos[i]] = hscan[goff[i]];
+  }
+}
+
+int launch_active_list(int64_t P, int64_t N, const GeomBufs& gb, const ScratchBufs& sb, uint32_t* flags,
+                       uint32_t* scan_tmp, uint32_t* total, int32_t* ids, uint32_t* hrow, int64_t* count,
+                       hipStream_t s) {
+  if (P <= 0) {
+    GSLM_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(int64_t), s));
+    GSLM_HIP_CHECK(hipMemsetAsync(hrow, 0, sizeof(uint32_t), s));
+    return GSLM_OK;
+  }
+  const unsigned nb = (unsigned)((P + 255) / 256);
+  hipLaunchKernelGGL(k_active_flags, dim3(nb), dim3(256), 0, s, P, gb.tiles, gb.goff, sb.hscan, flags);
+  GSLM_LAUNCH_CHECK();
+  // in place, as the row map's own scan
+  const int st = exclusive_scan_u32(flags, nullptr, flags, P, scan_tmp, total, s);
+  if (st) return st;
+  hipLaunchKernelGGL(k_active_scatter, dim3(nb), dim3(256), 0, s, P, N, gb.tiles, gb.goff, sb.hscan, flags, total, ids,
+                     hrow, count);
+  GSLM_LAUNCH_CHECK();
+  return GSLM_OK;
+}
+
 // ---- the line search's shared binning (gslm_union_*) ----
 // The seven line-search points of train_jvp.py:262-280 differ only in the groups the LM step moves (xyz is masked,
 // :221-227), so one view's Gaussians keep their screen centre and depth order at every point and only their

@@ -115,31 +115,47 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(ViewK v, GaussK g, const
 // allows it runs 76 -> 71 us at 1M (the kernel is latency-bound: row sums, then the parameters, then the
 // vector groups).  The full-layout variant keeps the compiler's register count: forced to 96 VGPRs its SH-rest
 // epilogue spills and takes 0.18 -> 0.31 ms.
-template <bool WANT_MEANS, int ROWF4, bool PROJ>
+// ACTIVE (gslm_matvec_view_active): thread j handles Gaussian ids[j] of the scene (parameters, clamp word, tile
+// count) and row j of v and y, which hold the na listed Gaussians only.  The head rows of a block's 256 consecutive
+// listed Gaussians are still one contiguous range -- the Gaussians between them own none -- so the row sums and
+// their order are those of the full-layout kernel; their offsets come from the list's own hrow, read coalesced.
+template <bool WANT_MEANS, int ROWF4, bool PROJ, bool ACTIVE = false>
 __global__ __launch_bounds__(256, PROJ ? 5 : 1) void k_gather_lm(ViewK v, GaussK g, const uint32_t* __restrict__ clampw,
                                                     const uint32_t* __restrict__ tiles,
                                                     const uint32_t* __restrict__ goff,
                                                     const uint32_t* __restrict__ hscan,
-                                                    const float4* __restrict__ rows, FlatK o) {
+                                                    const float4* __restrict__ rows, FlatK o,
+                                                    const int32_t* __restrict__ ids, int64_t na,
+                                                    const uint32_t* __restrict__ hrow) {
   o.rest_proj = PROJ ? 1 : 0;  // the launcher picked the variant from it
   if (cg_stopped(v)) return;
   extern __shared__ __attribute__((aligned(16))) float s_rest[];  // row chunks, then the factored SH stage
   __shared__ double s_dot[4];
   const int tid = threadIdx.x;
-  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x;
-  const int64_t i = i0 + tid;
-  const int64_t nvalid = min((int64_t)blockDim.x, g.P - i0);
-  const uint32_t n = i < g.P ? tiles[i] : 0u;
+  const int64_t j0 = (int64_t)blockIdx.x * blockDim.x;
+  const int64_t j = j0 + tid;
+  const int64_t nrows = ACTIVE ? na : g.P;  // rows of v and y
+  const int64_t nvalid = min((int64_t)blockDim.x, nrows - j0);
+  const bool valid = j < nrows;
+  const int64_t i = ACTIVE ? (valid ? (int64_t)ids[j] : 0) : j;
+  // (a listed Gaussian owns a head row, so it touches a tile: its tile count is not read)
+  const uint32_t n = ACTIVE ? (valid ? 1u : 0u) : (valid ? tiles[i] : 0u);
   float G2[NV];
-  {
+  if (ACTIVE) {
+    // the list's own row offsets (k_active_scatter): entry j's head rows are [hrow[j], hrow[j + 1])
+    const uint32_t R0 = hrow[j0], R1 = hrow[j0 + nvalid];
+    const uint32_t h0 = valid ? hrow[j] : R1, h1 = valid ? hrow[j + 1] : R1;
+    block_sum_rows<ROWF4>(rows, R0, R1, h0, h1 - h0, reinterpret_cast<float4*>(s_rest), G2);
+  } else {
     // this Gaussian's head rows (the LM row map): [hscan[goff], hscan[goff + tiles])
-    const int64_t il = i0 + nvalid - 1;
-    const uint32_t R0 = hscan[goff[i0]], R1 = hscan[goff[il] + tiles[il]];
-    const uint32_t h0 = i < g.P ? hscan[goff[i]] : R1, h1 = i < g.P ? hscan[goff[i] + n] : R1;
+    const int64_t il = j0 + nvalid - 1;
+    const uint32_t R0 = hscan[goff[j0]], R1 = hscan[goff[il] + tiles[il]];
+    const uint32_t h0 = valid ? hscan[goff[i]] : R1, h1 = valid ? hscan[goff[i] + n] : R1;
     block_sum_rows<ROWF4>(rows, R0, R1, h0, h1 - h0, reinterpret_cast<float4*>(s_rest), G2);
   }
   ChainOut co;
-  if (i < g.P) chain_vjp<true>(v, g, i, n != 0, n ? clampw[i] : 0u, G2, WANT_MEANS, co);
+  if (valid) chain_vjp<true>(v, g, i, n != 0, n ? clampw[i] : 0u, G2, WANT_MEANS, co);
+  if (ACTIVE) g.P = na;  // the epilogue writes rows j < na of y (it reads P and M of g only)
   lm_epilogue<WANT_MEANS, true>((v.D + 1) * (v.D + 1), g, co, o, s_rest, s_dot);
 }
 
@@ -232,27 +248,93 @@ int launch_preprocess_bwd(const ViewK& v, const GaussK& g, const GeomBufs& gb, c
 
 int launch_gather_lm(const ViewK& v, const GaussK& g, const GeomBufs& gb, const ScratchBufs& sb, const GradK& y,
                      const GradK& vin, const double* damp7, bool overwrite, bool mask_xyz, double* dot_part,
-                     hipStream_t s, bool rest_proj) {
-  if (g.P == 0) return GSLM_OK;
+                     hipStream_t s, bool rest_proj, const int32_t* ids, int64_t na, const uint32_t* hrow) {
+  const bool active = na >= 0;
+  const int64_t nrows = active ? na : g.P;
+  if (nrows == 0) return GSLM_OK;
   FlatK o;
   const int st = make_flatk(g, y, vin, damp7, overwrite, dot_part, &o, rest_proj);
   if (st) return st;
-  const unsigned nb = (unsigned)((g.P + 255) / 256);
+  if (active && (!mask_xyz || !ids || !hrow)) {
+    set_error("internal: the active-list gather runs on the LM rows (mask_xyz)");
+    return GSLM_ERR_INVALID;
+  }
+  const unsigned nb = (unsigned)((nrows + 255) / 256);
   const size_t rest_lds = sh_stage_floats<true>(g.M) * sizeof(float);
   const size_t chunk_lds = (size_t)GATHER_CHUNK * (mask_xyz ? 2 : 3) * sizeof(float4);
   const size_t lds = (rest_lds > chunk_lds ? rest_lds : chunk_lds) + 16;
-  if (mask_xyz && o.rest_proj)
+  if (active && o.rest_proj)
+    hipLaunchKernelGGL((k_gather_lm<false, 2, true, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles,
+                       gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow);
+  else if (active)
+    hipLaunchKernelGGL((k_gather_lm<false, 2, false, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles,
+                       gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow);
+  else if (mask_xyz && o.rest_proj)
     hipLaunchKernelGGL((k_gather_lm<false, 2, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o);
+                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr);
   else if (mask_xyz)
     hipLaunchKernelGGL((k_gather_lm<false, 2, false>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o);
+                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr);
   else if (o.rest_proj)
     hipLaunchKernelGGL((k_gather_lm<true, 3, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o);
+                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr);
   else
     hipLaunchKernelGGL((k_gather_lm<true, 3, false>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o);
+                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr);
+  GSLM_LAUNCH_CHECK();
+  return GSLM_OK;
+}
+
+// ---- flat vectors between the P layout and an active list's (gslm_active_pack / gslm_active_unpack) ----
+struct PackK {
+  int w[8];        // floats per row of each group
+  int64_t poff[8]; // first float of each group in the P layout
+  int64_t aoff[8]; // ... in the list's layout
+  int n;
+  int wsum;
+};
+// element e = (list row j, float c of the row's wsum floats over all groups), TO_ACTIVE: dst[list] = src[P layout]
+template <bool TO_ACTIVE>
+__global__ __launch_bounds__(256) void k_active_pack(PackK k, const int32_t* __restrict__ ids, int64_t na,
+                                                      const float* __restrict__ src, float* __restrict__ dst) {
+  const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (e >= na * k.wsum) return;
+  const int64_t j = e / k.wsum;
+  int c = (int)(e - j * k.wsum), grp = 0;
+  while (grp < k.n - 1 && c >= k.w[grp]) c -= k.w[grp++];
+  const int64_t full = k.poff[grp] + (int64_t)ids[j] * k.w[grp] + c;
+  const int64_t act = k.aoff[grp] + j * k.w[grp] + c;
+  if (TO_ACTIVE) dst[act] = src[full];
+  else dst[full] = src[act];
+}
+
+int launch_active_pack(bool to_active, const float* src, float* dst, const int32_t* ids, int64_t na, int64_t P,
+                       const int32_t* widths, int ngroups, int64_t tail_n, hipStream_t s) {
+  if (ngroups < 1 || ngroups > 8 || !widths || na < 0 || na > P || tail_n < 0 || !src || !dst || (na > 0 && !ids)) {
+    set_error("active pack: 1..8 groups, 0 <= n_active <= P, non-NULL buffers");
+    return GSLM_ERR_INVALID;
+  }
+  PackK k{};
+  int64_t po = 0, ao = 0;
+  for (int q = 0; q < ngroups; ++q) {
+    if (widths[q] < 0) { set_error("active pack: negative group width"); return GSLM_ERR_INVALID; }
+    k.w[q] = widths[q];
+    k.poff[q] = po;
+    k.aoff[q] = ao;
+    po += P * widths[q];
+    ao += na * widths[q];
+    k.wsum += widths[q];
+  }
+  k.n = ngroups;
+  const int64_t src_n = to_active ? po : ao, dst_n = to_active ? ao : po;
+  if (!to_active) GSLM_HIP_CHECK(hipMemsetAsync(dst, 0, (size_t)dst_n * sizeof(float), s));  // +0.0f off the list
+  if (tail_n > 0)
+    GSLM_HIP_CHECK(hipMemcpyAsync(dst + dst_n, src + src_n, (size_t)tail_n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  const int64_t total = na * k.wsum;
+  if (total == 0) return GSLM_OK;
+  const unsigned nb = (unsigned)((total + 255) / 256);
+  if (to_active) hipLaunchKernelGGL(k_active_pack<true>, dim3(nb), dim3(256), 0, s, k, ids, na, src, dst);
+  else hipLaunchKernelGGL(k_active_pack<false>, dim3(nb), dim3(256), 0, s, k, ids, na, src, dst);
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
 }

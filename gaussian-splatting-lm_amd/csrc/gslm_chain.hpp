@@ -380,15 +380,17 @@ __device__ __forceinline__ void write_grads(const GaussK& g, const GradK& o, int
 
 // Forward mode: tangent of the render record from input tangents t (NULL = 0).
 // out: [dx_pix, dy_pix, dconic a, b, c, dopacity_eff, dr, dg, db, dinvdepth]
+// it: the row of Gaussian i in the tangent's groups (t, m2t) -- i itself, or its position in an active list
+// (gslm_matvec_view_active), where the tangent vectors hold the listed Gaussians only.
 template <bool RAW>
 __device__ __forceinline__ void chain_jvp(const ViewK& v, const GaussK& g, const GaussK& t, const float* m2t,
-                                          int64_t i, uint32_t clamped, float T2[10]) {
+                                          int64_t i, int64_t it, uint32_t clamped, float T2[10]) {
   Geo e;
   compute_geo<RAW>(v, g, i, clamped, e);
   float dm[3] = {0.f, 0.f, 0.f};
   if (t.means3D)
 #pragma unroll
-    for (int k = 0; k < 3; ++k) dm[k] = t.means3D[3 * i + k];
+    for (int k = 0; k < 3; ++k) dm[k] = t.means3D[3 * it + k];
   const float dtx = (v.view[0] * dm[0] + v.view[4] * dm[1]) + v.view[8] * dm[2];
   const float dty = (v.view[1] * dm[0] + v.view[5] * dm[1]) + v.view[9] * dm[2];
   const float dtz = (v.view[2] * dm[0] + v.view[6] * dm[1]) + v.view[10] * dm[2];
@@ -403,8 +405,8 @@ __device__ __forceinline__ void chain_jvp(const ViewK& v, const GaussK& g, const
     dpy += (pm[4 * j + 1] * e.p_w - pm[4 * j + 3] * mul2) * dm[j];
   }
   if (m2t) {
-    dpx += m2t[3 * i + 0];
-    dpy += m2t[3 * i + 1];
+    dpx += m2t[3 * it + 0];
+    dpy += m2t[3 * it + 1];
   }
   T2[0] = dpx * (0.5f * (float)v.W);
   T2[1] = dpy * (0.5f * (float)v.H);
@@ -413,15 +415,15 @@ __device__ __forceinline__ void chain_jvp(const ViewK& v, const GaussK& g, const
   float dS[6];
   if (g.cov3D) {
 #pragma unroll
-    for (int k = 0; k < 6; ++k) dS[k] = t.cov3D ? t.cov3D[6 * i + k] : 0.f;
+    for (int k = 0; k < 6; ++k) dS[k] = t.cov3D ? t.cov3D[6 * it + k] : 0.f;
   } else {
     float ds[3] = {0.f, 0.f, 0.f}, dq[4] = {0.f, 0.f, 0.f, 0.f};
     if (t.scales)
 #pragma unroll
-      for (int k = 0; k < 3; ++k) ds[k] = RAW ? e.s[k] * t.scales[3 * i + k] : t.scales[3 * i + k];
+      for (int k = 0; k < 3; ++k) ds[k] = RAW ? e.s[k] * t.scales[3 * it + k] : t.scales[3 * it + k];
     if (t.rot) {
 #pragma unroll
-      for (int k = 0; k < 4; ++k) dq[k] = t.rot[4 * i + k];
+      for (int k = 0; k < 4; ++k) dq[k] = t.rot[4 * it + k];
       if (RAW) {
         const float qd = ((e.q[0] * dq[0] + e.q[1] * dq[1]) + e.q[2] * dq[2]) + e.q[3] * dq[3];
 #pragma unroll
@@ -488,14 +490,14 @@ __device__ __forceinline__ void chain_jvp(const ViewK& v, const GaussK& g, const
     aa_grad(e, ha, hb, hc);
     dh = ha * dc00 + hb * dc01 + hc * dc11;
   }
-  float dop = t.opac ? t.opac[i] : 0.f;
+  float dop = t.opac ? t.opac[it] : 0.f;
   if (RAW) dop = e.op * (1.f - e.op) * dop;
   T2[5] = dop * e.h + e.op * dh;
 
   // colour
   if (g.colors) {
 #pragma unroll
-    for (int ch = 0; ch < 3; ++ch) T2[6 + ch] = t.colors ? t.colors[3 * i + ch] : 0.f;
+    for (int ch = 0; ch < 3; ++ch) T2[6 + ch] = t.colors ? t.colors[3 * it + ch] : 0.f;
   } else {
     float dres[3] = {0.f, 0.f, 0.f};
     const int nc = (v.D + 1) * (v.D + 1);
@@ -505,10 +507,10 @@ __device__ __forceinline__ void chain_jvp(const ViewK& v, const GaussK& g, const
       if (t.rest_R) {
         // SH-rest coordinates c_j in the orthonormal basis Q of span{B_rest(dir_b)}: B_rest(dir)^T Q c = sum_j R[j][col] c_j
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) dres[ch] += B[0] * t.sh(i, 0, ch);
+        for (int ch = 0; ch < 3; ++ch) dres[ch] += B[0] * t.sh(it, 0, ch);
         if (t.rest && nc > 1) {
           const float* Rc = t.rest_R + i * rest_basis_floats(t.rest_V) + rest_basis_floats(t.rest_col);
-          const float* c = t.rest + (i - t.rest_base) * t.rest_stride;
+          const float* c = t.rest + (it - t.rest_base) * t.rest_stride;
 #pragma unroll
           for (int j = 0; j < MAX_REST_VIEWS; ++j)
             if (j <= t.rest_col) {
@@ -520,18 +522,18 @@ __device__ __forceinline__ void chain_jvp(const ViewK& v, const GaussK& g, const
       } else if (t.rest_proj) {
         // projected SH-rest tangent: sum_k B_k v_k = |B_rest| c for v = (B_rest / |B_rest|) (x) c
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) dres[ch] += B[0] * t.sh(i, 0, ch);
+        for (int ch = 0; ch < 3; ++ch) dres[ch] += B[0] * t.sh(it, 0, ch);
         if (t.rest && nc > 1) {
           const float nb = sh_rest_norm(B, nc);
 #pragma unroll
-          for (int ch = 0; ch < 3; ++ch) dres[ch] += nb * t.rest[(i - t.rest_base) * t.rest_stride + ch];
+          for (int ch = 0; ch < 3; ++ch) dres[ch] += nb * t.rest[(it - t.rest_base) * t.rest_stride + ch];
         }
       } else {
 #pragma unroll
         for (int k = 0; k < 16; ++k)
           if (k < nc && (k == 0 || t.rest)) {
 #pragma unroll
-            for (int ch = 0; ch < 3; ++ch) dres[ch] += B[k] * t.sh(i, k, ch);
+            for (int ch = 0; ch < 3; ++ch) dres[ch] += B[k] * t.sh(it, k, ch);
           }
       }
     }

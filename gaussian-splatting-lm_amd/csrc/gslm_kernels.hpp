@@ -499,6 +499,11 @@ int launch_binning(const ViewK& v, int64_t P, const GeomBufs& gb, const BinBufs&
                    bool device_count = false, uint32_t* n_out = nullptr);
 int launch_lm_rowmap(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const ImgBufs& ib, const ScratchBufs& sb,
                      int64_t N, hipStream_t s);
+// the ascending ids of the Gaussians that own a head row of the LM row map and their row offsets hrow [count + 1]
+// (gslm_active_list); flags [P] doubles as the scan's output, scan_tmp: scan_tmp_bytes(P), total: one word
+int launch_active_list(int64_t P, int64_t N, const GeomBufs& gb, const ScratchBufs& sb, uint32_t* flags,
+                       uint32_t* scan_tmp, uint32_t* total, int32_t* ids, uint32_t* hrow, int64_t* count,
+                       hipStream_t s);
 int launch_point_ids(const uint32_t* point_list, int64_t N, uint32_t* out, hipStream_t s);
 // amask (or NULL): the blend visits by the union list's per-set masks (bits `shift` .. shift + 3 of amask[k],
 // k_duplicate_union) with the records of gb (that set's geometry) instead of the point list's own quadrant bits
@@ -568,8 +573,10 @@ struct XpbyK {
   int64_t xoff;
 };
 // compact: the LM rows' 8-float tangent records (store_trec, tangent.hip) instead of 12 floats
+// na >= 0 (gslm_matvec_view_active): one thread per listed Gaussian; t's and xp's groups hold the na listed rows
 int launch_tangent_pre(const ViewK& v, const GaussK& g, const GaussK& t, const float* m2t, const GeomBufs& gb,
-                       const ScratchBufs& sb, const XpbyK* xp, hipStream_t s, bool compact);
+                       const ScratchBufs& sb, const XpbyK* xp, hipStream_t s, bool compact,
+                       const int32_t* ids = nullptr, int64_t na = -1);
 int launch_rowsum_screen(const GaussK& g, const GeomBufs& gb, const ScratchBufs& sb, float* out, hipStream_t s);
 constexpr int MAX_SCREEN_VIEWS = 16;
 constexpr int MAX_REST_VIEWS = GSLM_MAX_REST_VIEWS;
@@ -605,7 +612,11 @@ int launch_matvec_render(const ViewK& v, const GaussK& t, const GeomBufs& gb, co
                          hipStream_t s);
 int launch_gather_lm(const ViewK& v, const GaussK& g, const GeomBufs& gb, const ScratchBufs& sb, const GradK& y,
                      const GradK& vin, const double* damp7, bool overwrite, bool mask_xyz, double* dot_part,
-                     hipStream_t s, bool rest_proj = false);
+                     hipStream_t s, bool rest_proj = false, const int32_t* ids = nullptr, int64_t na = -1,
+                     const uint32_t* hrow = nullptr);
+// a flat vector's groups ([rows x widths[k]], then a copied tail) between the P layout and an active list's
+int launch_active_pack(bool to_active, const float* src, float* dst, const int32_t* ids, int64_t na, int64_t P,
+                       const int32_t* widths, int ngroups, int64_t tail_n, hipStream_t s);
 int launch_sh_rest_project(const ViewK& v, const GaussK& g, int mode, const float* in, int64_t in_stride, float* out,
                            int64_t out_stride, hipStream_t s);
 }  // namespace gslm

@@ -101,16 +101,20 @@ __device__ __forceinline__ void store_trec(float4* __restrict__ out, int64_t i, 
   }
 }
 
-template <bool RAW, bool XPBY>
+// ACTIVE (gslm_matvec_view_active): thread j handles Gaussian ids[j] of the scene (parameters, clamp word, tile
+// count, tangent record) and row j of the tangent's groups and of the fused direction update, which hold the na
+// listed Gaussians only.  Same arithmetic per Gaussian as the full-layout kernel.
+template <bool RAW, bool XPBY, bool ACTIVE = false>
 __global__ __launch_bounds__(256) void k_preprocess_jvp(ViewK v, GaussK g, GaussK t, const float* __restrict__ m2t,
                                                          const uint32_t* __restrict__ clampw,
                                                          const uint32_t* __restrict__ tiles,
                                                          float4* __restrict__ trec, XpbyK xp, int compact,
-                                                         int lead) {
+                                                         int lead, const int32_t* __restrict__ ids, int64_t na) {
   extern __shared__ __attribute__((aligned(16))) float s_rest[];  // XPBY: [256 * 3(M-1)]; lead >= 0: [256 * rest_stride]
   if (cg_stopped(v)) return;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (!XPBY && lead >= 0) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t n = ACTIVE ? na : g.P;  // rows of the tangent's groups
+  if (!XPBY && !ACTIVE && lead >= 0) {
     // the drop-in JVP: the block's primal SH rows through LDS (per-thread reads at a 3M-float stride touch a line
     // per lane per load; stage_lead)
     stage_sh_rows(g, lead, s_rest);
@@ -119,49 +123,63 @@ __global__ __launch_bounds__(256) void k_preprocess_jvp(ViewK v, GaussK g, Gauss
     // the direction this kernel reads is the updated one: each thread reads back only its own
     // Gaussian's elements, all written by this block before the barrier; its SH-rest tangent (the
     // bulk of them, 3(M-1) floats at a 180-B stride) from the LDS copy instead of memory
-    block_xpby(xp, g.P, s_rest);
+    block_xpby(xp, n, s_rest);
     __syncthreads();
     if (t.rest) {
       t.rest = s_rest;
       t.rest_base = (int64_t)blockIdx.x * blockDim.x;
     }
   }
-  if (i >= g.P) return;
-  if (tiles[i] == 0) return;  // never gathered by the render passes
+  if (j >= n) return;
+  const int64_t i = ACTIVE ? (int64_t)ids[j] : j;
+  if (!ACTIVE && tiles[i] == 0) return;  // never gathered by the render passes (a listed Gaussian always is)
   float T2[10];
-  chain_jvp<RAW>(v, g, t, m2t, i, clampw[i], T2);
+  chain_jvp<RAW>(v, g, t, m2t, i, j, clampw[i], T2);
   store_trec(trec, i, T2, compact != 0);
 }
 
 // ------------------------------------------------------------------ launcher
 int launch_tangent_pre(const ViewK& v, const GaussK& g, const GaussK& t, const float* m2t, const GeomBufs& gb,
-                       const ScratchBufs& sb, const XpbyK* xp, hipStream_t s, bool compact) {
-  // P = 0 with a fused direction update: one block still applies the flat tail's update (block_xpby)
-  if (g.P == 0 && !(xp && xp->tail_p)) return GSLM_OK;
-  const unsigned nb = (unsigned)((g.P + 255) / 256) + (g.P == 0 ? 1u : 0u);
+                       const ScratchBufs& sb, const XpbyK* xp, hipStream_t s, bool compact, const int32_t* ids,
+                       int64_t na) {
+  const bool active = na >= 0;
+  const int64_t n = active ? na : g.P;
+  // no rows with a fused direction update: one block still applies the flat tail's update (block_xpby)
+  if (n == 0 && !(xp && xp->tail_p)) return GSLM_OK;
+  const unsigned nb = (unsigned)((n + 255) / 256) + (n == 0 ? 1u : 0u);
   XpbyK none{};
   const XpbyK& x = xp ? *xp : none;
+  if (active && (!g.raw || m2t || (na > 0 && !ids))) {
+    set_error("internal: the active-list tangent runs on raw leaves without a means2D tangent");
+    return GSLM_ERR_INVALID;
+  }
   if (xp) {
     if (t.rest && (t.rest != xp->p[2] || t.rest_stride != xp->w[2])) {
       set_error("internal: fused xpby expects the tangent's SH-rest group to be p's");
       return GSLM_ERR_INVALID;
     }
     const size_t lds = (size_t)256 * xp->w[2] * sizeof(float);
-    if (g.raw)
+    if (active)
+      hipLaunchKernelGGL((k_preprocess_jvp<true, true, true>), dim3(nb), dim3(256), lds, s, v, g, t, m2t, gb.clampw,
+                         gb.tiles, sb.trec, x, compact ? 1 : 0, -1, ids, na);
+    else if (g.raw)
       hipLaunchKernelGGL((k_preprocess_jvp<true, true>), dim3(nb), dim3(256), lds, s, v, g, t, m2t, gb.clampw, gb.tiles,
-                         sb.trec, x, compact ? 1 : 0, -1);
+                         sb.trec, x, compact ? 1 : 0, -1, nullptr, -1);
     else
       hipLaunchKernelGGL((k_preprocess_jvp<false, true>), dim3(nb), dim3(256), lds, s, v, g, t, m2t, gb.clampw, gb.tiles,
-                         sb.trec, x, compact ? 1 : 0, -1);
+                         sb.trec, x, compact ? 1 : 0, -1, nullptr, -1);
+  } else if (active) {
+    hipLaunchKernelGGL((k_preprocess_jvp<true, false, true>), dim3(nb), dim3(256), 0, s, v, g, t, m2t, gb.clampw,
+                       gb.tiles, sb.trec, x, compact ? 1 : 0, -1, ids, na);
   } else {
     const int lead = g.P > 0 ? stage_lead(g) : -1;
     const size_t lds = lead >= 0 ? (size_t)256 * g.rest_stride * sizeof(float) : 0;
     if (g.raw)
       hipLaunchKernelGGL((k_preprocess_jvp<true, false>), dim3(nb), dim3(256), lds, s, v, g, t, m2t, gb.clampw, gb.tiles,
-                         sb.trec, x, compact ? 1 : 0, lead);
+                         sb.trec, x, compact ? 1 : 0, lead, nullptr, -1);
     else
       hipLaunchKernelGGL((k_preprocess_jvp<false, false>), dim3(nb), dim3(256), lds, s, v, g, t, m2t, gb.clampw, gb.tiles,
-                         sb.trec, x, compact ? 1 : 0, lead);
+                         sb.trec, x, compact ? 1 : 0, lead, nullptr, -1);
   }
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
@@ -197,7 +215,7 @@ __global__ __launch_bounds__(256) void k_tangent_views(ViewsK vs, GaussK g, Gaus
     if (!(f >> 31)) continue;
     t.rest_col = view_base + b;  // SH-rest coordinates: this view's column of R
     float T2[10];
-    chain_jvp<true>(vs.v[b], g, t, nullptr, i, f & 7u, T2);
+    chain_jvp<true>(vs.v[b], g, t, nullptr, i, i, f & 7u, T2);
     store_trec(out, (int64_t)b * ostride + i, T2, compact != 0);
   }
 }

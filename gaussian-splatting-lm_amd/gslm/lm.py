@@ -15,6 +15,7 @@ vectors with its scalars in device memory (gslm_dot / gslm_axpy_dev / gslm_xpby_
 `check=False` an iteration has no host synchronisation at all.  CGLS on (J, D) and CG on A generate
 the same iterates in exact arithmetic; the reference's restart schedule and stopping tests are kept.
 """
+import copy
 import ctypes
 import math
 import os
@@ -46,7 +47,40 @@ class ViewRaster:
         self.geom = self.binning = self.image = self.scratch = None
         # the scratch's gradient rows of never-blended entries hold the zeros of an earlier fused
         # product on the current geometry (GSLM_MV_TAIL_CLEAN): false after a forward or a backward
+        self._active = None
         self.tail_clean = False
+        self.epoch = 0  # forwards so far: a right-hand side belongs to the geometry of one of them
+
+    @property
+    def tail_clean(self):
+        return self._tail_clean
+
+    @tail_clean.setter
+    def tail_clean(self, value):
+        self._tail_clean = bool(value)
+        if not value:
+            self._active = None  # the active list is the row map's: it lives exactly as long
+
+    def active_list(self, P, stream):
+        """(ids, Pa): the ascending int32 ids of the Gaussians that own a head row of this view's LM row map
+        (gslm_active_list) and their number -- the Gaussians whose column of this view's J is not identically
+        zero.  Needs the row map of an earlier product (tail_clean); built once per geometry (one read-back) and
+        kept until the next forward or backward."""
+        if not self.tail_clean or self.N is None:
+            raise RuntimeError("active_list: no current LM row map (run a product or rhs() on this geometry first)")
+        if self._active is None:
+            dev = self.device
+            ids = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+            rows = torch.empty(P + 1, dtype=torch.int32, device=dev)
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            work = _lib.u8(lib.gslm_active_list_bytes(P), dev)
+            check(lib.gslm_active_list(self.geom.data_ptr(), P, self.N, self.scratch.data_ptr(), self.scratch.numel(),
+                                       work.data_ptr(), work.numel(), ids.data_ptr(), rows.data_ptr(),
+                                       count.data_ptr(), stream), "gslm_active_list")
+            n = int(count.item())
+            self._active = (ids[:n], n)
+            self.active_rows = rows[:n + 1]  # entry j's head rows: [rows[j], rows[j + 1])
+        return self._active
 
     def forward(self, g, stream, want_invdepth=True):
         """The full forward (the drop-in's gslm_preprocess + gslm_rasterize).  want_invdepth=False: the LM paths,
@@ -54,6 +88,7 @@ class ViewRaster:
         P = g.P
         dev = self.device
         self.tail_clean = False
+        self.epoch += 1
         if self.geom is None or self.geom.numel() < lib.gslm_geom_bytes(P):
             self.geom = _lib.u8(lib.gslm_geom_bytes(P), dev)
             self.image = _lib.u8(lib.gslm_image_bytes(self.H, self.W), dev)
@@ -88,6 +123,7 @@ class ViewRaster:
             raise RuntimeError("forward_dev: the workspaces of an earlier forward() at this P are required")
         P = g.P
         self.tail_clean = False
+        self.epoch += 1
         self.N = None
         check(lib.gslm_preprocess(ctypes.byref(self.view), ctypes.byref(g), self.geom.data_ptr(), self.geom.numel(),
                                   self.radii.data_ptr(), stream), "gslm_preprocess")
@@ -220,23 +256,29 @@ class LMProblem:
         if self.layout.rest_projected:
             full = torch.zeros(self.full_layout.numel, dtype=torch.float32, device=self.device)
             self.rhs_full(full)
-            return self._mark_rhs(self.project(full, out))
-        return self._mark_rhs(self.rhs_full(out))
+            return self._mark_rhs(self.project(full, out), fused=False)
+        return self._mark_rhs(self.rhs_full(out), fused=False)
 
-    def _mark_rhs(self, out):
+    def _mark_rhs(self, out, fused=True):
         """Remember the J^T b this problem produced (exposure slice zeroed): cgls_fused may then skip the exposure
         slice's D v in every product without checking it (exposure_is_zero)."""
         self._rhs_token = (out.data_ptr(), out._version)
+        # (the fused gather's J^T b is zero off the view's active list by construction: zero_off_active)
+        self._rhs_epochs = [vr.epoch for vr in self.views] if fused else None
         return out
 
     def exposure_is_zero(self, g):
         """Whether the exposure slice of the right-hand side g is zero, so that every CG iterate's is (J has no
         exposure column): true without a device read for the rhs() this problem produced and nobody modified
         since; otherwise checked on the device (one host sync per solve)."""
-        if getattr(self, "_rhs_token", None) == (g.data_ptr(), g._version):
+        if self.rhs_is_mine(g):
             return True
         e0, e1 = self.layout.offsets["exposure"]
         return not bool(g[e0:e1].any())
+
+    def rhs_is_mine(self, g):
+        """g is the J^T b this problem's rhs() produced, unmodified since."""
+        return getattr(self, "_rhs_token", None) == (g.data_ptr(), g._version)
 
     def rhs_full(self, out):
         """J^T b through the drop-in gslm_backward, in the reference's layout (full_layout)."""
@@ -353,11 +395,7 @@ class LMProblem:
             if self.ssim:
                 self._ssim_product(b, vr, g, vs, ys, opts)
                 continue
-            check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(vs),
-                                          self.weights[b].data_ptr(), int(self.mask_xyz), vr.geom.data_ptr(),
-                                          vr.binning.data_ptr(), vr.N, vr.image.data_ptr(), vr.scratch.data_ptr(),
-                                          vr.scratch.numel(), ctypes.byref(ys), ctypes.byref(opts), self.stream),
-                  "gslm_matvec_view_ex")
+            self._view_product(vr, g, vs, self.weights[b].data_ptr(), ys, opts, "gslm_matvec_view_ex")
             vr.tail_clean = True
         if exposure_zero:
             pass  # y[e0:e1] = D v[e0:e1] = 0 already (matvec_dot)
@@ -366,6 +404,23 @@ class LMProblem:
         else:
             y[e0:e1].zero_()
         return y
+
+    def _view_product(self, vr, g, vs, weight, ys, opts, what):
+        """gslm_matvec_view_ex on one view -- or, on an active_view() (v and y hold the listed Gaussians only),
+        gslm_matvec_view_active."""
+        if self._active is not None:
+            ids, na = self._active
+            check(lib.gslm_matvec_view_active(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(vs), weight,
+                                              int(self.mask_xyz), vr.geom.data_ptr(), vr.binning.data_ptr(), vr.N,
+                                              vr.image.data_ptr(), vr.scratch.data_ptr(), vr.scratch.numel(),
+                                              ctypes.byref(ys), ctypes.byref(opts), ids.data_ptr() if na else None,
+                                              vr.active_rows.data_ptr(), na, self.stream),
+                  what.replace("_ex", "_active"))
+            return
+        check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(vs), weight,
+                                      int(self.mask_xyz), vr.geom.data_ptr(), vr.binning.data_ptr(), vr.N,
+                                      vr.image.data_ptr(), vr.scratch.data_ptr(), vr.scratch.numel(), ctypes.byref(ys),
+                                      ctypes.byref(opts), self.stream), what)
 
     # pre = (s, beta_num, beta_den[, x, alpha_num, alpha_den]): before the product, [x += alpha v then]
     # v = s + beta v -- the CG direction update (and the deferred x update) of the previous iteration
@@ -399,16 +454,13 @@ class LMProblem:
         jv, u = self._jv[b], self._u[b]
         o1 = _lib.GslmMatvecOpts()
         o1.stages = 1 | 2  # TANGENT | RENDER
-        o1.flags = self.mv_flags
+        o1.flags = (MV_TAIL_CLEAN if vr.tail_clean else 0) | self.mv_flags  # (read by the active-list form only)
         o1.jv_out = jv.data_ptr()
         o1.xpby_s, o1.beta_num, o1.beta_den = opts.xpby_s, opts.beta_num, opts.beta_den
         o1.xpby_tail_v, o1.xpby_tail_s, o1.xpby_tail_n = opts.xpby_tail_v, opts.xpby_tail_s, opts.xpby_tail_n
         o1.alpha_num, o1.alpha_den, o1.xpby_x_offset = opts.alpha_num, opts.alpha_den, opts.xpby_x_offset
         o1.cg_ctl = opts.cg_ctl
-        check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(vs), jv.data_ptr(), 1,
-                                      vr.geom.data_ptr(), vr.binning.data_ptr(), vr.N, vr.image.data_ptr(),
-                                      vr.scratch.data_ptr(), vr.scratch.numel(), ctypes.byref(ys), ctypes.byref(o1),
-                                      self.stream), "gslm_matvec_view_ex(jv)")
+        self._view_product(vr, g, vs, jv.data_ptr(), ys, o1, "gslm_matvec_view_ex(jv)")
         check(lib.gslm_ssim_normal(vr.H, vr.W, self.gts[b].data_ptr(), self.ssim_state[b].data_ptr(), jv.data_ptr(),
                                    u.data_ptr(), self.stream), "gslm_ssim_normal")
         o2 = _lib.GslmMatvecOpts()
@@ -418,10 +470,7 @@ class LMProblem:
         o2.damp7 = opts.damp7
         o2.dot_vy, o2.dot_scratch, o2.dot_scratch_bytes = opts.dot_vy, opts.dot_scratch, opts.dot_scratch_bytes
         o2.cg_ctl = opts.cg_ctl
-        check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(vs), u.data_ptr(), 1,
-                                      vr.geom.data_ptr(), vr.binning.data_ptr(), vr.N, vr.image.data_ptr(),
-                                      vr.scratch.data_ptr(), vr.scratch.numel(), ctypes.byref(ys), ctypes.byref(o2),
-                                      self.stream), "gslm_matvec_view_ex(seed)")
+        self._view_product(vr, g, vs, u.data_ptr(), ys, o2, "gslm_matvec_view_ex(seed)")
         vr.tail_clean = True
 
     # -------------------------------------------------------------- view-sharded exchange (gslm.parallel)
@@ -535,6 +584,70 @@ class LMProblem:
         self._apply_mask(out)
         return out
 
+    # -------------------------------------------------------------- the active set (cgls_fused)
+    _active = None  # (ids, Pa) on an active_view(): the layout's rows are the listed Gaussians
+
+    def active_view(self):
+        """This problem restricted to the Gaussians its one view can move (ViewRaster.active_list): a shallow copy
+        whose layout is ParamLayout(Pa, ...) and whose products run gslm_matvec_view_active on the shared geometry.
+        A Gaussian off the list has an exactly zero column of J, so A = J^T W J + D is D there, and a CG solve from
+        x0 = 0 whose right-hand side is zero off the list keeps every vector exactly zero there: the solve on the
+        listed rows is the same solve (either residual: the SSIM product runs the same per-Gaussian stages).  pack /
+        unpack convert flat vectors.  None when it does not apply (several views, xyz unmasked, no current row
+        map, nothing visible)."""
+        if len(self.views) != 1 or not self.mask_xyz or self._active is not None:
+            return None
+        vr = self.views[0]
+        if not vr.tail_clean or vr.N is None:
+            return None
+        ids, na = vr.active_list(self.layout.P, self.stream)
+        if na == 0:
+            return None  # (every vector of the solve is the exposure tail alone: nothing to save)
+        act = copy.copy(self)
+        act._active = (ids, na)
+        act._full = self
+        act.layout = ParamLayout(na, self.layout.K, self.layout.n_exposure, rest_projected=self.layout.rest_projected)
+        act._bounds, act._damps = act.layout.group_damp_arrays(self.damp)
+        return act
+
+    def _pack_args(self):
+        lay = self._full.layout
+        widths = [3, 3, 3 * lay.rest_rows if lay.K > 1 else 0, 3, 4, 1]
+        return (ctypes.c_int32 * 6)(*widths), 6, lay.offsets["exposure"][1] - lay.offsets["exposure"][0]
+
+    def pack(self, full):
+        """The listed rows of a flat vector of the full problem's layout, in this view's layout."""
+        ids, na = self._active
+        w, n, tail = self._pack_args()
+        out = torch.empty(self.layout.numel, dtype=torch.float32, device=full.device)
+        check(lib.gslm_active_pack(full.data_ptr(), out.data_ptr(), ids.data_ptr(), na, self._full.layout.P, w, n, tail,
+                                   self.stream), "gslm_active_pack")
+        return out
+
+    def unpack(self, vec):
+        """A vector of this view's layout in the full problem's (zero off the list)."""
+        ids, na = self._active
+        w, n, tail = self._pack_args()
+        out = torch.empty(self._full.layout.numel, dtype=torch.float32, device=vec.device)
+        check(lib.gslm_active_unpack(vec.data_ptr(), out.data_ptr(), ids.data_ptr(), na, self._full.layout.P, w, n,
+                                     tail, self.stream), "gslm_active_unpack")
+        return out
+
+    def zero_off_active(self, g):
+        """Whether the full-layout right-hand side g is zero on every Gaussian off the list: true without a device
+        read for the rhs() this problem produced and nobody modified since (the fused gather sums no rows for those
+        Gaussians); otherwise checked on the device (one read-back)."""
+        full = self._full
+        if full.rhs_is_mine(g) and full._rhs_epochs == [vr.epoch for vr in full.views]:
+            return True
+        ids, na = self._active
+        off = torch.ones(full.layout.P, dtype=torch.bool, device=g.device)
+        off[ids.long()] = False
+        for name, v in full.layout.views(g).items():
+            if name != "exposure" and v.numel() and bool((v.reshape(full.layout.P, -1)[off] != 0).any()):
+                return False
+        return True
+
     # -------------------------------------------------------------- device scalar algebra
     def dot(self, a, b, out_slot, damped=False):
         if damped:
@@ -573,6 +686,27 @@ def raise_nonfinite(prob, g, what="the normal-equations product (J^T J + D) p"):
     raise NonFiniteError(f"NaN detected in {what} during CGLS (J^T b is finite)")
 
 
+def _active_view_for(prob, g, callback):
+    """The active-set view of cgls_fused's problem (LMProblem.active_view) when the solve may run on it, else None."""
+    if callback is not None or os.environ.get("GSLM_CG_ACTIVE", "1") == "0":
+        return None
+    local = prob
+    if not isinstance(local, LMProblem):
+        from gslm import parallel
+        # a view-sharded operator without collectives delegates every product to its local problem
+        if not (isinstance(local, parallel.ShardedOperator) and not parallel.collectives_on(local.world_size)):
+            return None
+        local = local.local
+        if not isinstance(local, LMProblem):
+            return None
+    if g.numel() != local.layout.numel:
+        return None
+    act = local.active_view()
+    if act is None or not act.zero_off_active(g):
+        return None
+    return act
+
+
 def cgls_fused(prob, g, max_iter=10, restart_iter=10, tol=1e-10, atol=0.0, check_every=True, verbose=False,
                callback=None, host_checks=None):
     """cgls_damped (conjugate_gradient.py:51-127) on the fused operator, x0 = 0.
@@ -583,7 +717,21 @@ def cgls_fused(prob, g, max_iter=10, restart_iter=10, tol=1e-10, atol=0.0, check
     whole max_iter x restart_iter schedule and a stopped solve's remaining launches return at once);
     host_checks=True (or verbose / a callback, which need the values each iteration) reads the scalars back
     every iteration instead.  Both give the same iterates, stop and history.  With check_every=False the tests
-    are skipped (benchmark mode); the iterates are identical while no test fires."""
+    are skipped (benchmark mode); the iterates are identical while no test fires.
+
+    A local single-view problem with the xyz mask is solved on the Gaussians its view can move (LMProblem.
+    active_view: the rows of every CG vector that are exactly zero throughout are left out of the vectors, so the
+    per-Gaussian kernels stream Pa rows instead of P); x comes back in the full layout.  GSLM_CG_ACTIVE=0 keeps
+    the full vectors.  Not taken with a callback (it sees the solver's own vectors), for several views or the
+    Gaussian-sharded operators."""
+    act = _active_view_for(prob, g, callback)
+    if act is not None:
+        gp = act.pack(g)
+        if prob.exposure_is_zero(g):
+            act._mark_rhs(gp)  # (exposure_is_zero of the packed vector without a device read)
+        x, info = cgls_fused(act, gp, max_iter=max_iter, restart_iter=restart_iter, tol=tol, atol=atol,
+                             check_every=check_every, verbose=verbose, callback=None, host_checks=host_checks)
+        return act.unpack(x), info
     n = prob.layout.numel
     dev = prob.device
     st = prob.stream

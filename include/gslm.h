@@ -337,6 +337,43 @@ int gslm_matvec_view_ex(const gslm_view* view, const gslm_gaussians* g, const gs
 int gslm_sh_rest_project(const gslm_view* view, const gslm_gaussians* g, int32_t mode, const float* in,
                          int64_t in_stride, float* out, int64_t out_stride, void* stream);
 
+/* ---- The single-view product on the Gaussians the view can move (additive entry points, still ABI 9: no
+ * existing struct or signature changes) ----
+ * A Gaussian that owns no head row in the LM row map (GSLM_MV_TAIL_CLEAN above) is visited by no wave of the
+ * RENDER stage: its column of this view's J is exactly zero, so J^T W J + D acts on it as D alone, and a CG
+ * solve from x0 = 0 whose right-hand side is zero there keeps s, p, q and x exactly zero on it.  The ACTIVE
+ * Gaussians are the others; the per-Gaussian stages can run on vectors that hold the active Gaussians only.
+ *
+ * gslm_active_list: ids_dev[0 .. *count_dev) = the ascending ids i with at least one head row, from the row map a
+ * RENDER stage built for this geometry and binning (valid exactly while GSLM_MV_TAIL_CLEAN may be passed; the
+ * list depends on the geometry only), and rows_dev[0 .. *count_dev] = their row offsets: list entry j's head rows
+ * are [rows_dev[j], rows_dev[j + 1]) (the Gaussians between two listed ones own none).  ids_dev holds P entries,
+ * rows_dev P + 1; work is a device workspace of gslm_active_list_bytes(P) bytes.  Stream ordered, no
+ * synchronisation: read *count_dev back after it. */
+size_t gslm_active_list_bytes(int64_t P);
+int gslm_active_list(const void* geom, int64_t P, int64_t num_rendered, const void* scratch, size_t scratch_bytes,
+                     void* work, size_t work_bytes, int32_t* ids_dev, uint32_t* rows_dev, int64_t* count_dev,
+                     void* stream);
+/* gslm_matvec_view_ex on an active list (active_ids, active_rows: gslm_active_list's two outputs; mask_xyz only;
+ * not the SCREEN stage, trec_in or rest_basis): every group of v, y and xpby_s (and x at xpby_x_offset) is
+ * [n_active x width] -- row j belongs to Gaussian active_ids[j] -- while g, geom, binning and scratch stay the
+ * scene's.  TANGENT and GATHER run one thread per list entry; RENDER
+ * is the same launch.  Per-element arithmetic is that of gslm_matvec_view_ex: with v zero off the list, y here is
+ * bitwise the rows active_ids of the full product's y (dot_vy sums the same products in another grouping).
+ * dot_scratch >= gslm_dot_scratch_bytes(n_active).  Requires GSLM_MV_TAIL_CLEAN (the list comes from that map). */
+int gslm_matvec_view_active(const gslm_view* view, const gslm_gaussians* g, const gslm_grads* v,
+                            const float* pixel_weight, int32_t mask_xyz, const void* geom, const void* binning,
+                            int64_t num_rendered, const void* image, void* scratch, size_t scratch_bytes,
+                            const gslm_grads* y, const gslm_matvec_opts* opts, const int32_t* active_ids,
+                            const uint32_t* active_rows, int64_t n_active, void* stream);
+/* Flat param-space vectors between the P layout and the n_active layout: ngroups consecutive groups of
+ * [rows x widths[k]] floats followed by a flat tail of tail_n floats (copied).  pack: dst row j of every group =
+ * src row active_ids[j].  unpack: the reverse, every other row of dst written +0.0f.  ngroups <= 8. */
+int gslm_active_pack(const float* src, float* dst, const int32_t* active_ids, int64_t n_active, int64_t P,
+                     const int32_t* widths, int32_t ngroups, int64_t tail_n, void* stream);
+int gslm_active_unpack(const float* src, float* dst, const int32_t* active_ids, int64_t n_active, int64_t P,
+                       const int32_t* widths, int32_t ngroups, int64_t tail_n, void* stream);
+
 /* ---- view-sharded exchange (multi-GPU LM product), SURVEY 8(e) ----
  * Instead of all-reducing the param-space partial J^T W J v (F = 59 floats per Gaussian at SH 3),
  * every rank all-gathers per-view screen-space sums (8 floats per Gaussian per view) and applies the
@@ -552,6 +589,13 @@ int gslm_densify_stats(int64_t P, const float* means2D_grad, int64_t grad_stride
 int gslm_inspect(const void* geom, int64_t P, const void* binning, int64_t num_rendered, int32_t H, int32_t W,
                  const void* image, uint32_t* point_list, uint32_t* ranges, uint32_t* tiles_touched,
                  float* final_T, uint32_t* n_contrib, float* records, void* stream);
+
+/* The LM row map of the last RENDER stage on this geometry (valid while GSLM_MV_TAIL_CLEAN may be passed), copied
+ * device to device: goff [P] u32 (first goff-order slot of each Gaussian's tiles_touched entries) and hscan
+ * [num_rendered + 1] u32 (head entries among the slots before each) -- Gaussian i's head rows are
+ * [hscan[goff[i]], hscan[goff[i] + tiles_touched[i]]).  Either output may be NULL.  Additive, still ABI 9. */
+int gslm_inspect_rowmap(const void* geom, int64_t P, int64_t num_rendered, const void* scratch, size_t scratch_bytes,
+                        uint32_t* goff, uint32_t* hscan, void* stream);
 
 /* Device self-test of the wave primitives (one 64-lane wave).  in: [64][8] floats, out: [64].
  * which = 0: transposed 8-value reduction (lane l returns the sum of value (l >> 3) & 7);
