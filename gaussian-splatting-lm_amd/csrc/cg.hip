@@ -181,18 +181,27 @@ __global__ __launch_bounds__(DOT_THREADS) void k_cg_update(int64_t n, const doub
 // Failure detection first (the NaN asserts of matvec_T, solver_functions.py:125-130): a non-finite gamma, gamma',
 // delta, <x, g> or <x, s> -- a NaN or Inf anywhere in J^T b, in a product (J^T J + D) p or in the iterate reaches
 // these dots -- sets stop = 4 (GSLM_CG_STOP_NONFINITE) and nothing else; the host raises before the step is used.
+// Order: gamma and delta (written before the update) first, then delta < 1e-20, then the update's three dots -- on a
+// small delta k_cg_update<true> wrote no partials and k_dot_final3 summed stale scratch into them, so they are not
+// read on that path (the host-side tests of gslm.lm.cgls_fused also test delta first).
 // Same double arithmetic as the host-side tests of gslm.lm.cgls_fused.
 __global__ void k_cg_monitor(const double* __restrict__ gam, const double* __restrict__ gamn,
                              const double* __restrict__ del, const double* __restrict__ xg,
                              const double* __restrict__ xs, const double* __restrict__ b2, double tol, double atol,
                              double* __restrict__ ctl, int max_hist) {
   if (threadIdx.x != 0 || ctl[0] != 0.0) return;
-  if (!(isfinite(*gam) && isfinite(*gamn) && isfinite(*del) && isfinite(*xg) && isfinite(*xs))) {
+  if (!(isfinite(*gam) && isfinite(*del))) {
     ctl[0] = 4.0;
     return;
   }
+  // before gamma', <x, g>, <x, s> are looked at: the update that would have written them returned early on this
+  // delta (no partials), so they are sums over whatever the scratch held
   if (*del < 1e-20) {
     ctl[0] = 1.0;
+    return;
+  }
+  if (!(isfinite(*gamn) && isfinite(*xg) && isfinite(*xs))) {
+    ctl[0] = 4.0;
     return;
   }
   const double res = (*b2 - *xg) - *xs;

@@ -112,9 +112,9 @@ inline size_t scan_tmp_bytes(int64_t n) { return align_up((size_t)scan_blocks(n)
 int exclusive_scan_u32(const uint32_t* in, const uint32_t* idx, uint32_t* out, int64_t n, uint32_t* tmp,
                        uint32_t* total, hipStream_t s, int64_t inline_max_blocks = SCAN_INLINE_MAX_BLOCKS);
 // out_a[i] = sum_{j<i} in[j], out_b[i] = sum_{j<i} b[j] in one pass (tmp: scan_tmp_bytes(n)), b = in_b, or in
-// gathered through idx when in_b is NULL.
+// gathered through idx when in_b is NULL.  inline_max_blocks as in exclusive_scan_u32.
 int exclusive_scan_u32_dual(const uint32_t* in, const uint32_t* idx, uint32_t* out_a, uint32_t* out_b, int64_t n,
                             uint32_t* tmp, uint32_t* total_a, uint32_t* total_b, hipStream_t s,
-                            const uint32_t* in_b = nullptr);
+                            const uint32_t* in_b = nullptr, int64_t inline_max_blocks = SCAN_INLINE_MAX_BLOCKS);
 
 }  // namespace gslm

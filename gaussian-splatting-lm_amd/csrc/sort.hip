@@ -520,7 +520,8 @@ __global__ __launch_bounds__(SCAN_THREADS) void k_scan2_apply(const uint32_t* __
 }  // namespace
 
 int exclusive_scan_u32_dual(const uint32_t* in, const uint32_t* idx, uint32_t* out_a, uint32_t* out_b, int64_t n,
-                            uint32_t* tmp, uint32_t* total_a, uint32_t* total_b, hipStream_t s, const uint32_t* in_b) {
+                            uint32_t* tmp, uint32_t* total_a, uint32_t* total_b, hipStream_t s, const uint32_t* in_b,
+                            int64_t inline_max_blocks) {
   if (n <= 0) {
     GSLM_HIP_CHECK(hipMemsetAsync(total_a, 0, 4, s));
     GSLM_HIP_CHECK(hipMemsetAsync(total_b, 0, 4, s));
@@ -528,7 +529,7 @@ int exclusive_scan_u32_dual(const uint32_t* in, const uint32_t* idx, uint32_t* o
   }
   const int nb = (int)scan_blocks(n);
   hipLaunchKernelGGL(k_scan2_reduce, dim3(nb), dim3(SCAN_THREADS), 0, s, in, idx, in_b, n, tmp);
-  if (nb > SCAN_INLINE_MAX_BLOCKS) {
+  if (nb > inline_max_blocks) {
     hipLaunchKernelGGL(k_scan_top, dim3(2), dim3(256), 0, s, tmp, nb);
     hipLaunchKernelGGL(k_scan2_apply<true>, dim3(nb), dim3(SCAN_THREADS), 0, s, in, idx, in_b, n, tmp, out_a, out_b,
                        total_a, total_b);

@@ -467,8 +467,10 @@ int gslm_cg_update_monitor(int64_t n, const double* gam_dev, const double* del_d
  * [stop, iters, last_res, n_hist, history[max_hist]], initialised by the caller to [0, 0, +inf, 0, ...]:
  *   *del < 1e-20 -> stop = 1;  res = (*b2 - *xg) - *xs is appended to history;  res > last_res -> stop = 2;
  *   *gam_new < max(tol sqrt(*gam), atol) -> stop = 3;  otherwise iters += 1.
- * Checked before those: any of *gam, *gam_new, *del, *xg, *xs not finite -> stop = 4 (GSLM_CG_STOP_NONFINITE; the
- * reference's NaN asserts, solver/solver_functions.py:125-130) -- the caller must not use the iterate.
+ * Any of *gam, *gam_new, *del, *xg, *xs not finite -> stop = 4 (GSLM_CG_STOP_NONFINITE; the reference's NaN
+ * asserts, solver/solver_functions.py:125-130) -- the caller must not use the iterate.  *gam and *del are checked
+ * before everything else; *gam_new, *xg, *xs after the *del < 1e-20 test (gslm_cg_update_monitor leaves them
+ * undefined on such a delta).
  * Once stop != 0 every later gslm_cg_monitor / gslm_cg_update_monitor / product with opts->cg_ctl is a no-op. */
 #define GSLM_CG_STOP_NONFINITE 4
 int gslm_cg_monitor(const double* gam_dev, const double* gam_new_dev, const double* del_dev, const double* xg_dev,
@@ -607,6 +609,13 @@ int gslm_selftest(int32_t which, const float* in, float* out, void* stream);
  * up to a multiple of 256. */
 int gslm_selftest_scan(const uint32_t* in, uint32_t* out, int64_t n, int32_t force_top, void* tmp, size_t tmp_bytes,
                        uint32_t* total, void* stream);
+/* The same for the dual scan (the binning's two offset sequences in one pass): out_a[i] = sum_{j<i} in[j] and
+ * out_b[i] = sum_{j<i} b[j], with b = in_b, or in gathered through idx (a permutation of [0, n)) when in_b is NULL;
+ * exactly one of idx and in_b is given.  *total_a, *total_b = the two sums.  tmp as gslm_selftest_scan (it holds
+ * both sequences' block sums). */
+int gslm_selftest_scan_dual(const uint32_t* in, const uint32_t* idx, const uint32_t* in_b, uint32_t* out_a,
+                            uint32_t* out_b, int64_t n, int32_t force_top, void* tmp, size_t tmp_bytes,
+                            uint32_t* total_a, uint32_t* total_b, void* stream);
 
 const char* gslm_last_error(void);
 int gslm_abi_version(void);
