@@ -23,6 +23,134 @@ def make_scene(name, device="cpu"):
     return model, cams
 
 
+# ---- LM scenes with a visible background, saturated pixels and alpha masks (tests/test_gpu_lm_background.py,
+# tests/test_oracle_lm_background.py).  name -> (P, sh_degree, W, H, s0, model seed, camera seed)
+LM_BG_SCENES = {
+    "sh2_64x48": (1500, 2, 64, 48, 0.04, 90, 4),
+    "sh3_40x33": (1500, 3, 40, 33, 0.04, 11, 4),   # ragged on both axes
+    "sh1_33x17": (600, 1, 33, 17, 0.06, 11, 4),    # one tile plus one pixel on each axis
+}
+BG_WHITE = (1.0, 1.0, 1.0)       # the reference's white_background
+BG_GENERIC = (0.2, 0.5, 0.9)
+BG_ZERO = (0.0, 0.0, 0.0)
+# The model seeds are chosen (on the CPU oracle) so that in every scene and view whose GPU weights are compared with the
+# oracle's no covered pixel-channel lies within 4e-5 of the clamp's corners 0 and 1 (the tests assert 1e-5): the two
+# sides' 1[0 <= R <= 1] then agree whatever the host's or the GPU's rounding.
+OCCLUDER_SEED = 28
+
+
+def lm_bg_scene(name, n_views=1, occluders=False, seed=None, brighten=True):
+    """A synthetic scene whose every 2nd Gaussian is brightened (SH DC + 2..3, colour + 0.56..0.85) so that blended
+    pixels exceed 1 and the residual's clamp is active; random ground-truth images.  occluders: eight stacked
+    near-opaque Gaussians in front of the first camera and a quarter of the Gaussians behind it (as the "mixed" scenes
+    of tests/test_gpu_active_set.py, but leaving the background visible around the occluders), so that the view's
+    active list is a proper subset.  Returns (model, cams) on the CPU."""
+    from gslm.model import inverse_sigmoid
+    P, D, W, H, s0, seed0, cseed = LM_BG_SCENES[name]
+    seed = (OCCLUDER_SEED if occluders else seed0) if seed is None else seed
+    model = synthetic_gaussians(P, D, seed=seed, s0=s0, device="cpu", n_cams=n_views)
+    gen = torch.Generator().manual_seed(seed + 100)
+    cams = orbit_cameras(n_views, W, H, seed=cseed)
+    for i, c in enumerate(cams):
+        c.original_image = torch.rand(3, H, W, generator=torch.Generator().manual_seed(8 + i))
+    with torch.no_grad():
+        n = model._features_dc[::2].shape[0]
+        bright = 2.0 + torch.rand(n, 1, 1, generator=gen)  # (drawn either way: the draws below do not depend on it)
+        if brighten:
+            model._features_dc[::2] += bright
+        if occluders:
+            c = cams[0].camera_center.float()
+            f = -c / c.norm()  # orbit cameras look at the origin
+            perm = torch.randperm(P, generator=gen)
+            occ, out = perm[:8], perm[8:8 + P // 4]
+            jitter = 0.02 * (torch.rand(8, 3, generator=gen) - 0.5)
+            model._xyz[occ] = c + f * (1.2 + 0.01 * torch.arange(8.0)[:, None]) + jitter
+            model._scaling[occ] = math.log(0.2)
+            model._opacity[occ] = inverse_sigmoid(torch.tensor(0.999))
+            back = 0.5 + torch.rand(len(out), 1, generator=gen)
+            model._xyz[out] = c - f * back + 0.3 * (torch.rand(len(out), 3, generator=gen) - 0.5)
+    return model, cams
+
+
+# name -> (x0, y0, x1, y1) of the masks' block of exact zeros.  On the 64x48 scene it is two whole tiles (bottom right),
+# so a Gaussian whose tile rect lies inside touches masked-out pixels only; on the ragged scenes it cuts through tiles.
+ZERO_BLOCKS = {"sh2_64x48": (32, 32, 64, 48), "sh3_40x33": (21, 9, 37, 30), "sh1_33x17": (5, 3, 19, 12)}
+
+
+def lm_bg_mask(name, seed=0, block=True):
+    """A [1, H, W] alpha mask with values in [0.25, 0.95) and (block=True) ZERO_BLOCKS[name] of exact zeros."""
+    W, H = LM_BG_SCENES[name][2:4]
+    m = 0.25 + 0.7 * torch.rand(1, H, W, generator=torch.Generator().manual_seed(900 + seed))
+    if block:
+        x0, y0, x1, y1 = ZERO_BLOCKS[name]
+        m[:, y0:y1, x0:x1] = 0.0
+    return m
+
+
+def place_in_zero_block(model, cam, block, n=12, seed=0):
+    """Moves the first n Gaussians that are not brightened (odd index) in front of the camera so that they project
+    well inside `block` (whole tiles), and shrinks them (radius 2 px) so their tile rects stay inside it.  Returns
+    their ids."""
+    W, H = cam.image_width, cam.image_height
+    x0, y0, x1, y1 = block
+    assert x0 % 16 == 0 and y0 % 16 == 0 and x1 - x0 >= 12 and y1 - y0 >= 12
+    ids = torch.arange(1, 2 * n, 2)
+    gen = torch.Generator().manual_seed(700 + seed)
+    px = x0 + 5.0 + (x1 - x0 - 10.0) * torch.rand(n, generator=gen)
+    py = y0 + 5.0 + (y1 - y0 - 10.0) * torch.rand(n, generator=gen)
+    z = 2.0 + torch.rand(n, generator=gen)
+    fx, fy = W / (2.0 * math.tan(cam.FoVx * 0.5)), H / (2.0 * math.tan(cam.FoVy * 0.5))
+    pv = torch.stack([(px + 0.5 - 0.5 * W) / fx * z, (py + 0.5 - 0.5 * H) / fy * z, z, torch.ones(n)], dim=1)
+    world = pv @ torch.linalg.inv(cam.world_view_transform.float().cpu())  # row vectors: p_view = p_world @ V
+    with torch.no_grad():
+        model._xyz[ids] = world[:, :3]
+        model._scaling[ids] = math.log(0.005)
+    return ids
+
+
+def lm_bg_stats(model, cam, bg):
+    """What a background / saturation scene must exercise, measured on the oracle's render: the share of pixel-channels
+    with raw > 1, the share of pixels that are covered and still show the background (n_contrib > 0, T_final > 0.05),
+    and the number of covered pixel-channels within 1e-5 of the clamp's corners 0 and 1 (where the GPU's and the
+    oracle's 1[0 <= R <= 1] could fall on different sides through rounding)."""
+    a = activated(model)
+    st = oracle_settings(cam, model.active_sh_degree, torch.as_tensor(bg, dtype=a["means3D"].dtype))
+    with torch.no_grad():
+        raw, _, _, I = tr.rasterize(a["means3D"], torch.zeros_like(a["means3D"]), a["opacities"], st, shs=a["shs"],
+                                    scales=a["scales"], rotations=a["rotations"], return_internals=True)
+    covered = I["n_contrib"] > 0
+    near = ((raw - 1).abs() < 1e-5) | (raw.abs() < 1e-5)
+    return dict(saturated=float((raw > 1).float().mean()), below_zero=float((raw < 0).float().mean()),
+                background=float((covered & (I["final_T"] > 0.05)).float().mean()),
+                boundary=int((near & covered[None]).sum()), rect=I["pre"]["rect"], tiles=I["pre"]["tiles_touched"],
+                raw=raw)
+
+
+def assert_lm_bg_scene(model, cam, bg):
+    """The conditions every background / saturation scene must meet (on oracle data only); returns the stats."""
+    s = lm_bg_stats(model, cam, bg)
+    assert s["saturated"] >= 0.05, s["saturated"]
+    assert s["background"] >= 0.20, s["background"]
+    assert s["boundary"] == 0, s["boundary"]
+    return s
+
+
+def to_float64(model, cams):
+    """Deep copies of the model and cameras on the CPU in float64 (the oracle then runs in double)."""
+    import copy
+    mc = copy.deepcopy(model).to("cpu")
+    for t in mc.params():
+        t.data = t.data.double()
+    ccs = []
+    for c in cams:
+        cc = copy.deepcopy(c).to("cpu")
+        for k in ("original_image", "alpha_mask", "world_view_transform", "projection_matrix", "full_proj_transform",
+                  "camera_center"):
+            setattr(cc, k, getattr(cc, k).double())
+        ccs.append(cc)
+    return mc, ccs
+
+
 def activated(model):
     """The tensors render() hands to the rasterizer (gaussian_renderer/__init__.py:54-73)."""
     with torch.no_grad():
