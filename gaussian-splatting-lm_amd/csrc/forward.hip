@@ -468,13 +468,19 @@ static bool tile_order_xcd() {
   }();
   return on;
 }
-int launch_tile_order(int ntiles, const uint2* ranges, uint32_t* order, const uint32_t* cost, hipStream_t s) {
-  if (cost && tile_order_xcd())
+// one launcher for both forms (the tile passes' through launch_tile_order, gslm_selftest_tile_order's by its argument)
+int launch_tile_order_form(int form, int ntiles, const uint2* ranges, uint32_t* order, const uint32_t* cost,
+                           hipStream_t s) {
+  if (form == TILE_ORDER_XCD)
     hipLaunchKernelGGL(k_tile_order_xcd, dim3(1), dim3(1024), 0, s, ntiles, ranges, order, cost);
   else
     hipLaunchKernelGGL(k_tile_order, dim3(1), dim3(1024), 0, s, ntiles, ranges, order, cost);
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
+}
+int launch_tile_order(int ntiles, const uint2* ranges, uint32_t* order, const uint32_t* cost, hipStream_t s) {
+  return launch_tile_order_form(cost && tile_order_xcd() ? TILE_ORDER_XCD : TILE_ORDER_FLAT, ntiles, ranges, order, cost,
+                                s);
 }
 
 // Gaussian ids of the sorted list (mask bits stripped), for gslm_inspect.
@@ -516,6 +522,15 @@ __global__ __launch_bounds__(256) void k_ranges(int64_t N, const uint32_t* __res
     if (p != t[j]) ranges[t[j]].x = (uint32_t)(k0 + j);
     if (q != t[j]) ranges[t[j]].y = (uint32_t)(k0 + j + 1);
   }
+}
+// k_ranges over N sorted keys (the binnings', and gslm_selftest_ranges'): the ranges zeroed beforehand, N > 0
+int launch_ranges(int64_t N, const uint32_t* keys_sorted, uint2* ranges, const uint32_t* n_dev, uint32_t* n_out,
+                  hipStream_t s) {
+  if (N <= 0) return GSLM_OK;
+  const unsigned nbN = (unsigned)((N + 256 * RANGES_KEYS - 1) / (256 * RANGES_KEYS));
+  hipLaunchKernelGGL(k_ranges, dim3(nbN), dim3(256), 0, s, N, keys_sorted, ranges, n_dev, n_out);
+  GSLM_LAUNCH_CHECK();
+  return GSLM_OK;
 }
 
 // ---- the LM row map (ScratchBufs::hscan), once per geometry ----
@@ -886,10 +901,7 @@ int launch_union_binning(const ViewK& v, int64_t P, const GeomBufs& ug, const Bi
       set_error("internal: radix pass count disagrees with the union binning layout");
       return GSLM_ERR_INVALID;
     }
-    const unsigned nbN = (unsigned)((N + 256 * RANGES_KEYS - 1) / (256 * RANGES_KEYS));
-    hipLaunchKernelGGL(k_ranges, dim3(nbN), dim3(256), 0, s, N, bb.keys_sorted, bb.ranges, (const uint32_t*)nullptr,
-                       (uint32_t*)nullptr);
-    GSLM_LAUNCH_CHECK();
+    if ((st = launch_ranges(N, bb.keys_sorted, bb.ranges, nullptr, nullptr, s))) return st;
   }
   if (int st = launch_tile_order(ntiles, bb.ranges, bb.tile_order, nullptr, s)) return st;
   GSLM_LAUNCH_CHECK();
@@ -964,9 +976,7 @@ int launch_binning(const ViewK& v, int64_t P, const GeomBufs& gb, const BinBufs&
     set_error("internal: radix pass count disagrees with the binning layout");
     return GSLM_ERR_INVALID;
   }
-  const unsigned nbN = (unsigned)((N + 256 * RANGES_KEYS - 1) / (256 * RANGES_KEYS));
-  hipLaunchKernelGGL(k_ranges, dim3(nbN), dim3(256), 0, s, N, bb.keys_sorted, bb.ranges, n_dev, n_out);
-  GSLM_LAUNCH_CHECK();
+  if ((st = launch_ranges(N, bb.keys_sorted, bb.ranges, n_dev, n_out, s))) return st;
   if (int st = launch_tile_order(ntiles, bb.ranges, bb.tile_order, nullptr, s)) return st;
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;

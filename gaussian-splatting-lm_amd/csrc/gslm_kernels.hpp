@@ -497,6 +497,16 @@ int launch_preprocess_views(const PreViewsK& pv, const GaussK& g, const GeomBufs
 // NULL) receives the count
 int launch_binning(const ViewK& v, int64_t P, const GeomBufs& gb, const BinBufs& bb, int64_t N, hipStream_t s,
                    bool device_count = false, uint32_t* n_out = nullptr);
+// the binnings' per-tile [start, end) over N sorted tile ids (each below the size of ranges, which the caller has
+// zeroed: an absent tile stays [0, 0)); n_dev / n_out as launch_binning (n_out is written only with n_dev).  N <= 0
+// launches nothing.
+int launch_ranges(int64_t N, const uint32_t* keys_sorted, uint2* ranges, const uint32_t* n_dev, uint32_t* n_out,
+                  hipStream_t s);
+// the tile passes' launch order in the given form: the frame-wide longest-first order, or the XCD-banded one (the LM
+// product's; launch_tile_order in forward.hip picks between them)
+constexpr int TILE_ORDER_FLAT = 0, TILE_ORDER_XCD = 1;
+int launch_tile_order_form(int form, int ntiles, const uint2* ranges, uint32_t* order, const uint32_t* cost,
+                           hipStream_t s);
 int launch_lm_rowmap(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const ImgBufs& ib, const ScratchBufs& sb,
                      int64_t N, hipStream_t s);
 // the ascending ids of the Gaussians that own a head row of the LM row map and their row offsets hrow [count + 1]

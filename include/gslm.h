@@ -616,6 +616,45 @@ int gslm_selftest_scan(const uint32_t* in, uint32_t* out, int64_t n, int32_t for
 int gslm_selftest_scan_dual(const uint32_t* in, const uint32_t* idx, const uint32_t* in_b, uint32_t* out_a,
                             uint32_t* out_b, int64_t n, int32_t force_top, void* tmp, size_t tmp_bytes,
                             uint32_t* total_a, uint32_t* total_b, void* stream);
+/* Device self-tests of the three binning primitives behind every image (additive, still ABI 9): thin wrappers of the
+ * library's own launchers, all buffers device memory unless noted.
+ *
+ * gslm_selftest_sort: the stable LSD radix sort of (u32 key, u32 value) pairs on key bits [0, end_bit), 1 <= end_bit <=
+ * 32 (the tile sort, the depth sort, the union binning's payload sort, the k-NN cell sort): ceil(end_bit / 8) passes
+ * of ceil(end_bit / passes) bits, the last one the rest (13 bits: 7 + 6, not 8 + 5), keys equal on those bits keep their input order, and the bits at or above
+ * end_bit travel with their key unchanged.  k0 / v0 hold the input, k1 / v1 are their ping-pong partners, n words each;
+ * *result_in_alt (host) = 1 when the sorted pairs are in k1 / v1 (an odd pass count), 0 when in k0 / v0.
+ *   iota_values != 0: the values are the indices 0..n-1 and v0 is not read (it may be NULL).
+ *   last_gather (or NULL): a table the last pass reads -- the output key slot i holds last_gather[value i] in place of
+ *     the sorted key.
+ *   n_dev (or NULL, device u32): n is a capacity and the first min(n, *n_dev) pairs are sorted; nothing past that
+ *     count is written.
+ *   p0 / p1 (both or neither): a payload word per pair, moved with it; the result is in p1 exactly when *result_in_alt.
+ *   key_range != 0 (end_bit 32, no payload, no n_dev; refused otherwise): the depth sort's form, which sorts
+ *     key - min over the keys other than 0xFFFFFFFF in as many byte passes as that span needs and copies in the rest --
+ *     the same output as the plain 32-bit sort.
+ *   hist: gslm_selftest_sort_hist_bytes(n, payload != 0) bytes of scratch, 8-byte aligned.  On return its words
+ *     [256 nb, 256 nb + 256), nb = (bytes - 1040) / 1032, hold the last pass's count of keys per digit.
+ * GSLM_ERR_INVALID for n < 0, end_bit outside 1..32, a NULL buffer, one payload buffer without the other or a refused
+ * key_range combination; GSLM_ERR_CAPACITY for a short hist; nothing is launched then, or when n == 0. */
+size_t gslm_selftest_sort_hist_bytes(int64_t n, int32_t payload);
+int gslm_selftest_sort(uint32_t* k0, uint32_t* v0, uint32_t* k1, uint32_t* v1, uint32_t* p0, uint32_t* p1, int64_t n,
+                       int32_t end_bit, int32_t iota_values, int32_t key_range, const uint32_t* last_gather,
+                       const uint32_t* n_dev, void* hist, size_t hist_bytes, int32_t* result_in_alt, void* stream);
+/* gslm_selftest_ranges: the per-tile [start, end) of a sorted list of n tile ids, each below ntiles (keys: 16-byte
+ * aligned): ranges [ntiles][2] is zeroed, then tile t's pair set to its run of keys; an absent tile stays (0, 0).
+ * n_dev (or NULL): n is a capacity and the list the first min(n, *n_dev) keys (the rest are not read); n_out (or
+ * NULL, only with n_dev; not written when n == 0) then receives *n_dev itself, uncapped. */
+int gslm_selftest_ranges(const uint32_t* keys, int64_t n, int32_t ntiles, const uint32_t* n_dev, uint32_t* n_out,
+                         uint32_t* ranges, void* stream);
+/* gslm_selftest_tile_order: the tile passes' launch order, order [ntiles] a permutation of the tiles, by each tile's
+ * cost[t], or with cost == NULL its list length ranges[t][1] - ranges[t][0].  form 0: heaviest first over the whole
+ * frame, in buckets of the cost (exact below 768, 32 wide above, one bucket from 8928 on; arbitrary inside a bucket).
+ * form 1: the tiles cut in row-major order into 8 bands of about equal weight (cost + 1), each band heaviest first,
+ * and the bands interleaved -- entry 8 k + g is band g's k-th tile while every band still has one, the bands'
+ * leftovers follow band by band.  The form is the argument's, whatever GSLM_TILE_ORDER says. */
+int gslm_selftest_tile_order(const uint32_t* ranges, const uint32_t* cost, int32_t ntiles, int32_t form,
+                             uint32_t* order, void* stream);
 
 const char* gslm_last_error(void);
 int gslm_abi_version(void);

@@ -134,6 +134,72 @@ def test_union_binning_argument_checks():
                                         None) == _lib.GSLM_ERR_INVALID
 
 
+def test_binning_selftest_argument_checks():
+    """gslm_selftest_sort / _ranges / _tile_order (tests/test_gpu_binning_primitives.py runs them): bad counts, bit
+    ranges and forms, NULL buffers, half a payload pair, a short histogram workspace and the sort's own refusal of
+    key_range beside a payload, a device count or fewer than 32 bits all come back as error codes before any launch
+    (dummy pointers, never dereferenced: no GPU here)."""
+    from gslm import _lib
+    lib = _lib.lib
+    INV, CAP = _lib.GSLM_ERR_INVALID, _lib.GSLM_ERR_CAPACITY
+    # the workspace query: 256 counts per block, 256 totals, the key range's 4 words and a (min, max) pair per block;
+    # blocks of 2048 keys below 1024 blocks of 4096 and with a payload, of 4096 from there on
+    hb = lib.gslm_selftest_sort_hist_bytes
+    for n, payload, nb in ((0, 0, 0), (1, 0, 1), (2048, 0, 1), (2049, 0, 2), (4_190_208, 0, 2046), (4_190_209, 0, 1024),
+                           (8_388_609, 0, 2049), (4_194_305, 1, 2049), (2049, 1, 2)):
+        assert hb(n, payload) == 1032 * nb + 1040, (n, payload)
+    p, n = 4096, 100
+    h = hb(n, 0)
+    alt = ctypes.c_int32(7)
+    ra = ctypes.byref(alt)
+
+    def sort(k0=p, v0=p, k1=p, v1=p, p0=None, p1=None, n=n, end_bit=13, iota=0, key_range=0, gather=None, n_dev=None,
+             hist=p, hist_bytes=h, res=ra):
+        return lib.gslm_selftest_sort(k0, v0, k1, v1, p0, p1, n, end_bit, iota, key_range, gather, n_dev, hist,
+                                      hist_bytes, res, None)
+
+    assert sort(n=-1) == INV
+    for end_bit in (-1, 0, 33):
+        assert sort(end_bit=end_bit) == INV
+        assert b"end_bit" in lib.gslm_last_error()
+    for null in ("k0", "v0", "k1", "v1", "hist", "res"):
+        assert sort(**{null: None}) == INV, null
+        assert b"NULL" in lib.gslm_last_error()
+    assert sort(v1=None, iota=1) == INV  # iota_values spares v0 only
+    assert sort(p0=p) == INV and sort(p1=p) == INV
+    assert b"partner" in lib.gslm_last_error()
+    assert sort(hist_bytes=h - 1) == CAP
+    # a payload sort keeps the blocks of 2048 where the plain sort takes 4096: twice the blocks
+    assert sort(p0=p, p1=p, n=4_190_209, hist_bytes=hb(4_190_209, 0)) == CAP
+    assert alt.value == 7  # refused by the wrapper: the flag is not touched
+    assert sort(key_range=1, end_bit=32, p0=p, p1=p, hist_bytes=hb(n, 1)) == INV
+    assert b"key_range" in lib.gslm_last_error()
+    assert sort(key_range=1, end_bit=32, n_dev=p) == INV
+    assert sort(key_range=1, end_bit=24) == INV
+    assert sort(n=0, hist_bytes=hb(0, 0)) == _lib.GSLM_OK and alt.value == 0  # nothing to sort, nothing launched
+
+    def ranges(keys=p, n=n, ntiles=12, n_dev=None, n_out=None, out=p):
+        return lib.gslm_selftest_ranges(keys, n, ntiles, n_dev, n_out, out, None)
+
+    assert ranges(n=-1) == INV and ranges(n=1 << 32) == INV
+    assert ranges(ntiles=0) == INV and ranges(ntiles=-3) == INV
+    assert ranges(keys=None) == INV and ranges(out=None) == INV
+    assert ranges(n_out=p) == INV
+    assert b"n_out without n_dev" in lib.gslm_last_error()
+    assert ranges(keys=p + 4) == INV and ranges(out=p + 4) == INV
+    assert b"aligned" in lib.gslm_last_error()
+
+    def order(rng=p, cost=None, ntiles=12, form=0, out=p):
+        return lib.gslm_selftest_tile_order(rng, cost, ntiles, form, out, None)
+
+    assert order(ntiles=0) == INV and order(ntiles=-1) == INV
+    assert order(form=2) == INV and order(form=-1) == INV
+    assert order(out=None) == INV
+    assert order(rng=None) == INV and order(rng=None, cost=p, out=None) == INV
+    assert b"neither ranges nor cost" in lib.gslm_last_error()
+    assert order(rng=p + 4) == INV
+
+
 def test_dropin_modules_import_with_reference_names():
     import diff_gaussian_rasterization as d
     import diff_gaussian_rasterization.batch_render as b

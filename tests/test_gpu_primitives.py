@@ -1,4 +1,5 @@
-"""Device self-tests of the wave primitives and the sort/scan building blocks (through the C ABI)."""
+"""Device self-tests of the wave primitives and the scan building blocks (through the C ABI).  The radix sort, the tile
+ranges and the tile launch order have theirs in tests/test_gpu_binning_primitives.py."""
 import ctypes
 
 import pytest
