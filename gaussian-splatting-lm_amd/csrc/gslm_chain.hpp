@@ -501,13 +501,16 @@ __device__ __forceinline__ void chain_jvp(const ViewK& v, const GaussK& g, const
   } else {
     float dres[3] = {0.f, 0.f, 0.f};
     const int nc = (v.D + 1) * (v.D + 1);
-    if (t.dc) {
+    // either SH group may be NULL on its own (a zero tangent): the rest's is not dropped with a NULL dc
+    if (t.dc || t.rest) {
       float B[16];
       sh_basis(v.D, e.dir[0], e.dir[1], e.dir[2], B);
       if (t.rest_R) {
         // SH-rest coordinates c_j in the orthonormal basis Q of span{B_rest(dir_b)}: B_rest(dir)^T Q c = sum_j R[j][col] c_j
+        if (t.dc) {
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) dres[ch] += B[0] * t.sh(it, 0, ch);
+          for (int ch = 0; ch < 3; ++ch) dres[ch] += B[0] * t.sh(it, 0, ch);
+        }
         if (t.rest && nc > 1) {
           const float* Rc = t.rest_R + i * rest_basis_floats(t.rest_V) + rest_basis_floats(t.rest_col);
           const float* c = t.rest + (it - t.rest_base) * t.rest_stride;
@@ -521,8 +524,10 @@ __device__ __forceinline__ void chain_jvp(const ViewK& v, const GaussK& g, const
         }
       } else if (t.rest_proj) {
         // projected SH-rest tangent: sum_k B_k v_k = |B_rest| c for v = (B_rest / |B_rest|) (x) c
+        if (t.dc) {
 #pragma unroll
-        for (int ch = 0; ch < 3; ++ch) dres[ch] += B[0] * t.sh(it, 0, ch);
+          for (int ch = 0; ch < 3; ++ch) dres[ch] += B[0] * t.sh(it, 0, ch);
+        }
         if (t.rest && nc > 1) {
           const float nb = sh_rest_norm(B, nc);
 #pragma unroll
@@ -531,7 +536,7 @@ __device__ __forceinline__ void chain_jvp(const ViewK& v, const GaussK& g, const
       } else {
 #pragma unroll
         for (int k = 0; k < 16; ++k)
-          if (k < nc && (k == 0 || t.rest)) {
+          if (k < nc && (k == 0 ? t.dc != nullptr : t.rest != nullptr)) {
 #pragma unroll
             for (int ch = 0; ch < 3; ++ch) dres[ch] += B[k] * t.sh(it, k, ch);
           }

@@ -135,6 +135,105 @@ def assert_lm_bg_scene(model, cam, bg):
     return s
 
 
+# ---- the branch-heavy scene of the per-Gaussian chain tests (tests/chain_jacobian.py, tests/test_gpu_chain_rules.py,
+# tests/test_oracle_chain_jacobian.py)
+# per-axis scale factors of every Gaussian: a Gaussian with three nearly equal scales has a nearly zero rotation derivative,
+# and float32 rounding (of the oracle as of the kernels) then dominates any relative measure of it
+ANISOTROPY = (0.5, 1.0, 2.0)
+
+
+def chain_branch_scene(P=768, D=3, W=64, H=48, n_views=2, seed=5):
+    """A scene that runs the derivative branches of csrc/gslm_chain.hpp the standard scenes leave idle: Gaussians
+    outside the +-1.3 tan-FoV clamp (xyz spread to +-1.6 and every 4th Gaussian 0.25 wide, so they stay visible there),
+    Gaussians under the antialiasing clamp max(2.5e-5, det0 / det) (every 8th, offset 1: 4e-4 wide and anisotropic --
+    with equal scales the rotation derivative is exactly zero), SH colour clamps on every channel (every 3rd, offset 2,
+    darkened; the SH rest four times as strong), |q_raw| spread over 0.2 .. 6 instead of ~2, and every Gaussian's
+    scales spread by ANISOTROPY.  Random ground-truth images.  Returns (model, cams) on the CPU; what it must exercise is asserted by assert_chain_branch_scene."""
+    model = synthetic_gaussians(P, D, seed=seed, s0=0.04, device="cpu", n_cams=n_views)
+    cams = orbit_cameras(n_views, W, H, seed=4)
+    for i, c in enumerate(cams):
+        c.original_image = torch.rand(3, H, W, generator=torch.Generator().manual_seed(8 + i))
+    gen = torch.Generator().manual_seed(seed + 100)
+    with torch.no_grad():
+        model._xyz *= 1.6
+        n = model._scaling[::4].shape[0]
+        model._scaling[::4] = math.log(0.25) + 0.3 * torch.randn(n, 3, generator=gen)
+        n = model._scaling[1::8].shape[0]
+        model._scaling[1::8] = math.log(4e-4) + 0.4 * torch.randn(n, 3, generator=gen)
+        n = model._features_dc[2::3].shape[0]
+        model._features_dc[2::3] -= 1.2 * torch.rand(n, 1, 3, generator=gen)
+        model._features_rest *= 4.0
+        model._rotation *= 0.2 + 3.0 * torch.rand(P, 1, generator=gen)
+        model._scaling += torch.log(torch.tensor(ANISOTROPY))
+    return model, cams
+
+
+def sh_subset(model, max_degree, active_degree):
+    """A copy of the model that stores SH up to max_degree (the leading coefficients of the rest) with active_degree
+    active."""
+    import copy
+    m = copy.deepcopy(model)
+    K = (max_degree + 1) ** 2
+    m.set_params(m._xyz, m._features_dc, m._features_rest[:, :K - 1], m._scaling, m._rotation, m._opacity, m._exposure,
+                 requires_grad=True)
+    m.max_sh_degree, m.active_sh_degree = max_degree, active_degree
+    return m
+
+
+def chain_branch_stats(model, cam, aa, scale_modifier=1.0):
+    """The float64 oracle's per-Gaussian branch data of one view: preprocess's dict plus `outx` / `outy` (outside the
+    tan-FoV clamp), `under_aa` (det0 / det below the antialiasing clamp; computed whatever aa is), `near_fov` /
+    `near_aa` (relative distance to those thresholds), `res` (the SH colour + 0.5 before its clamp) and `boundary`
+    (Gaussians whose visibility decision lies within float32 rounding of flipping: the pre-ceil radius within 1e-4 of
+    an integer, a tile-rect bound within 1e-4 of a tile edge, or t.z within 1e-6 of 0.2)."""
+    mc, (cc,) = to_float64(model, [cam])
+    st = tr.settings_from_camera(cc, torch.zeros(3, dtype=torch.float64), mc.active_sh_degree,
+                                 scale_modifier=scale_modifier, antialiasing=aa)
+    with torch.no_grad():
+        xyz = mc.get_xyz
+        pre = tr.preprocess(xyz, torch.zeros_like(xyz), mc.get_opacity, mc.get_features, None, mc.get_scaling,
+                            mc.get_rotation, None, st)
+        pv = torch.cat([xyz, torch.ones(len(xyz), 1, dtype=xyz.dtype)], dim=1) @ cc.world_view_transform
+        limx, limy = 1.3 * st.tanfovx, 1.3 * st.tanfovy
+        rx, ry = (pv[:, 0] / pv[:, 2]).abs() / limx, (pv[:, 1] / pv[:, 2]).abs() / limy
+        a, b, c = pre["cov2d"].unbind(1)
+        det, det0 = a * c - b * b, (a - 0.3) * (c - 0.3) - b * b
+        ratio = det0 / det
+        d = xyz - cc.camera_center[None]
+        res = tr.eval_sh(st.sh_degree, mc.get_features, d / d.norm(dim=1, keepdim=True)) + 0.5
+        mid = 0.5 * (a + c)
+        r0 = 3.0 * torch.sqrt(mid + torch.sqrt(torch.clamp_min(mid * mid - det, 0.1)))
+        radius = torch.ceil(r0)
+
+        def near_int(t):
+            return (t - torch.round(t)).abs() < 1e-4
+        edges = [(pre["xy"][:, k] + s * radius + o) / 16.0 for k in (0, 1) for s, o in ((-1.0, 0.0), (1.0, 15.0))]
+        boundary = near_int(r0) | ((pv[:, 2] - 0.2).abs() < 1e-6)
+        for e in edges:
+            boundary |= near_int(e)
+    out = dict(pre)
+    out.update(outx=rx > 1, outy=ry > 1, near_fov=torch.minimum((rx - 1).abs(), (ry - 1).abs()),
+               under_aa=ratio < 0.000025, near_aa=(ratio / 0.000025 - 1).abs(), res=res, boundary=boundary)
+    return out
+
+
+def assert_chain_branch_scene(model, cam, aa, scale_modifier=1.0):
+    """The conditions the chain-rule tests rely on (on float64 oracle data only); returns chain_branch_stats.
+    Every branch is populated among the visible Gaussians, and no Gaussian sits so close to the tan-FoV limit or the
+    antialiasing threshold that float32 and float64 could take different sides of the branch."""
+    s = chain_branch_stats(model, cam, aa, scale_modifier)
+    vis = s["visible"]
+    P = vis.numel()
+    assert int((vis & (s["outx"] | s["outy"])).sum()) >= 10
+    for ch in range(3):
+        assert int((vis & s["clamped"][:, ch]).sum()) >= 50, ch
+    assert int((vis & s["under_aa"]).sum()) >= 40
+    assert P - int(vis.sum()) >= 60
+    assert int((s["near_fov"] < 1e-3).sum()) == 0
+    assert int((s["near_aa"] < 1e-2).sum()) == 0
+    return s
+
+
 def to_float64(model, cams):
     """Deep copies of the model and cameras on the CPU in float64 (the oracle then runs in double)."""
     import copy

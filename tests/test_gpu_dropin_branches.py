@@ -11,6 +11,8 @@ The reference's render() / batch_render() reach these through PipelineParams and
 Each case runs the forward (image 1e-4 L-inf, radii exact), the VJP (every input's gradient within 1e-4 of
 its max) and the JVP (colour / inverse-depth tangents within 1e-4 of their max) on the GPU and on the
 oracle (oracle/torch_raster.py, autograd / forward-AD) with the same inputs and tangents.
+The plain, antialiasing and scale_modifier cases also run on scenes.chain_branch_scene (Gaussians outside the tan-FoV
+clamp, under the antialiasing clamp, SH-clamped), at the same bounds.
 """
 import pytest
 import torch
@@ -35,8 +37,12 @@ CASES = {
 }
 
 
+def _case(case):
+    return CASES[case] if case in CASES else BRANCH_SCENE_CASES[case]
+
+
 def _inputs(model, case):
-    aa, smod, use_cov, use_col, split = CASES[case]
+    aa, smod, use_cov, use_col, split = _case(case)
     a = activated(model)
     out = {"means3D": a["means3D"], "opacities": a["opacities"]}
     if use_cov:
@@ -78,16 +84,41 @@ def _rel(a, b):
 
 
 def _settings(cam, D, case, bg):
-    aa, smod, use_cov, _, _ = CASES[case]
+    aa, smod, use_cov, _, _ = _case(case)
     # with cov3D_precomp the modifier is already inside the covariance; the rasterizer ignores it then
     return (oracle_settings(cam, D, bg, scale_modifier=smod, antialiasing=aa),
             gpu_settings(cam, D, bg, scale_modifier=smod, antialiasing=aa))
+
+
+# The branch-heavy scene of the per-Gaussian chain tests (scenes.chain_branch_scene; its conditions are asserted on the
+# oracle in _branch_scene): the RAW=false chains outside the tan-FoV clamp, under the antialiasing clamp and with SH
+# colour clamps, through the whole drop-in forward / backward / JVP.  "default" is the plain configuration.
+BRANCH_SCENE_CASES = {"default": (False, 1.0, False, False, False), "antialiasing": CASES["antialiasing"],
+                      "scale_modifier_0.8": CASES["scale_modifier_0.8"]}
+
+
+def _branch_scene(case):
+    from scenes import assert_chain_branch_scene, chain_branch_scene
+    model, cams = chain_branch_scene()
+    aa, smod = BRANCH_SCENE_CASES[case][:2]
+    assert_chain_branch_scene(model, cams[0], aa, smod)
+    return model, cams
 
 
 @pytest.mark.parametrize("scene", ["dense_2k_sh3_64x48", "mid_8k_sh1_96x80"])
 @pytest.mark.parametrize("case", list(CASES))
 def test_branch_forward_backward(scene, case):
     model, cams = make_scene(scene)
+    _check_forward_backward(model, cams, case)
+
+
+@pytest.mark.parametrize("case", list(BRANCH_SCENE_CASES))
+def test_branch_scene_forward_backward(case):
+    model, cams = _branch_scene(case)
+    _check_forward_backward(model, cams, case)
+
+
+def _check_forward_backward(model, cams, case):
     D = model.active_sh_degree
     cam = cams[0]
     bg = torch.tensor([0.25, 0.5, 0.75])
@@ -120,6 +151,16 @@ def test_branch_forward_backward(scene, case):
 @pytest.mark.parametrize("case", list(CASES))
 def test_branch_jvp(scene, case):
     model, cams = make_scene(scene)
+    _check_jvp(model, cams, case)
+
+
+@pytest.mark.parametrize("case", list(BRANCH_SCENE_CASES))
+def test_branch_scene_jvp(case):
+    model, cams = _branch_scene(case)
+    _check_jvp(model, cams, case)
+
+
+def _check_jvp(model, cams, case):
     D = model.active_sh_degree
     cam = cams[0]
     bg = torch.tensor([0.3, 0.1, 0.7])
