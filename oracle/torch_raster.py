@@ -250,31 +250,60 @@ def _tile_pixels(t, gx, H, W):
     return py.reshape(-1), px.reshape(-1)
 
 
-def _blend_tile(xy, conic, opac, rgb, invd, L, px, py, bg):
-    """Front-to-back blend of one tile's pixels over its sorted list L (upstream renderCUDA semantics).
-    Returns (color[npx,3], invdepth[npx], final_T[npx], n_contrib[npx] int32)."""
+def _decisions(power, araw):
+    """The skip / stop decisions of one tile's blend, frozen at the primal: power, araw [npx, n] (exponent and
+    unclamped alpha of every pixel x list entry).  Returns (contrib, last, ac, valid, Tincl, first_stop): the entries
+    each pixel blends, its n_contrib, the clamped alpha, the entries passing power <= 0 and alpha >= 1/255, the
+    transmittance the stop test sees after each entry, and the position each pixel stops at (n: never)."""
+    ac = torch.clamp_max(araw, 0.99)
+    valid = (power <= 0) & (ac >= 1.0 / 255.0)
+    om = torch.where(valid, 1 - ac, torch.ones_like(ac))
+    Tincl = torch.cumprod(om, dim=1)
+    stop = valid & (Tincl < 0.0001)
+    n = power.shape[1]
+    idx = torch.arange(n)[None, :].expand_as(stop)
+    first_stop = torch.where(stop, idx, torch.full_like(idx, n)).min(dim=1).values
+    contrib = valid & (idx < first_stop[:, None])
+    last = torch.where(contrib, idx + 1, torch.zeros_like(idx)).max(dim=1).values
+    return contrib, last, ac, valid, Tincl, first_stop
+
+
+def _power_alpha(xy, conic, opac, L, px, py):
     dtype = xy.dtype
-    npx = py.numel()
     pxf = px.to(dtype)[:, None]
     pyf = py.to(dtype)[:, None]
     dx = xy[L, 0][None, :] - pxf
     dy = xy[L, 1][None, :] - pyf
     a, b, c = conic[L, 0][None, :], conic[L, 1][None, :], conic[L, 2][None, :]
     power = -0.5 * (a * dx * dx + c * dy * dy) - b * dx * dy
-    G = torch.exp(power)
-    araw = opac[L][None, :] * G
+    return power, opac[L][None, :] * torch.exp(power)
+
+
+def tile_decisions(pre, point_list, ranges, t, H, W):
+    """What the blend of tile t decides on, for tests that need the distance of every decision from its threshold:
+    dict of [npx, n] tensors power, alpha_raw (before the 0.99 clamp), valid, test_T (the stop test's transmittance)
+    and seen (the entries the pixel evaluates: up to and including the one it stops at).  None for an empty tile."""
+    s, e = int(ranges[t, 0]), int(ranges[t, 1])
+    if e <= s:
+        return None
+    gx, _ = pre["grid"]
+    py, px = _tile_pixels(t, gx, H, W)
+    with torch.no_grad():
+        power, araw = _power_alpha(pre["xy"], pre["conic"], pre["opacity"], point_list[s:e], px, py)
+        _, _, _, valid, Tincl, first_stop = _decisions(power, araw)
+        idx = torch.arange(e - s)[None, :].expand_as(valid)
+    return dict(power=power, alpha_raw=araw, valid=valid, test_T=Tincl, seen=idx <= first_stop[:, None])
+
+
+def _blend_tile(xy, conic, opac, rgb, invd, L, px, py, bg):
+    """Front-to-back blend of one tile's pixels over its sorted list L (upstream renderCUDA semantics).
+    Returns (color[npx,3], invdepth[npx], final_T[npx], n_contrib[npx] int32)."""
+    dtype = xy.dtype
+    npx = py.numel()
+    power, araw = _power_alpha(xy, conic, opac, L, px, py)
     alpha = araw + (torch.clamp_max(araw, 0.99) - araw).detach()
     with torch.no_grad():
-        ac = torch.clamp_max(araw.detach(), 0.99)
-        valid = (power.detach() <= 0) & (ac >= 1.0 / 255.0)
-        om = torch.where(valid, 1 - ac, torch.ones_like(ac))
-        Tincl = torch.cumprod(om, dim=1)
-        stop = valid & (Tincl < 0.0001)
-        n = L.numel()
-        idx = torch.arange(n)[None, :].expand_as(stop)
-        first_stop = torch.where(stop, idx, torch.full_like(idx, n)).min(dim=1).values
-        contrib = valid & (idx < first_stop[:, None])
-        last = torch.where(contrib, idx + 1, torch.zeros_like(idx)).max(dim=1).values
+        contrib, last = _decisions(power.detach(), araw.detach())[:2]
     m = contrib.to(dtype)
     one_m = 1 - m * alpha
     Tin = torch.cumprod(one_m, dim=1)

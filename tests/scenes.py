@@ -234,6 +234,94 @@ def assert_chain_branch_scene(model, cam, aa, scale_modifier=1.0):
     return s
 
 
+# ---- scenes whose tile lists have a controlled depth (tests/blend_reference.py, tests/test_oracle_blend_depths.py,
+# tests/test_gpu_blend_depths.py)
+STACK_DZ = 0.002      # view-depth step between consecutive stack entries
+STACK_Z0 = 2.0
+STACK_SIGMA_PX = 14.0  # screen sigma of the middle ANISOTROPY axis
+BLOB_GRID = (1.0, 3.5, 6.0)
+WALL_POWER_MIN = 2.2e-4  # nominal: the perspective Jacobian off the axis widens the footprint, measured 1.2e-4
+
+
+def _world_from_pixel(cam, px, py, z):
+    """World positions of the points that project to pixel (px, py) at view depth z (float64 arithmetic, float32
+    result)."""
+    W, H = cam.image_width, cam.image_height
+    fx, fy = W / (2.0 * math.tan(cam.FoVx * 0.5)), H / (2.0 * math.tan(cam.FoVy * 0.5))
+    px, py, z = px.double(), py.double(), z.double()
+    pv = torch.stack([(px + 0.5 - 0.5 * W) / fx * z, (py + 0.5 - 0.5 * H) / fy * z, z, torch.ones_like(z)], dim=1)
+    world = pv @ torch.linalg.inv(cam.world_view_transform.double().cpu())  # row vectors: p_view = p_world @ V
+    return world[:, :3].float()
+
+
+def stack_scene(n, W, H, a=0.02, seed=0, blobs=None, wall=None, sigma_px=STACK_SIGMA_PX, jitter=0.15):
+    """n Gaussians stacked along the optical axis of orbit_cameras(1, W, H, seed=1)[0], entry i at view depth
+    STACK_Z0 + STACK_DZ i, so that every tile's sorted list is the index order and (every Gaussian reaching every pixel
+    with alpha >= 1/255) every tile's list depth is n.  Wide anisotropic Gaussians (ANISOTROPY around sigma_px
+    pixels, sigma_px of the middle axis), opacity a U[0.75, 1.25], SH degree 1, random rotations; the centres are
+    jittered perpendicular to the axis only, by at most `jitter` pixels around the pixel corner nearest the image centre
+    (a centre on a pixel would put that pixel's exponent at 0, the `power > 0` decision's edge).  Random ground-truth
+    image.
+
+    blobs=(q, k): the last 27 entries become small near-opaque Gaussians (sigma 2.5 px, opacity 0.97) on a 3x3 grid
+    inside quadrant q (pixels [8 (q & 1), +7] x [8 (q >> 1), +7]) of tile 0, three deep, between stack entries k - 1
+    and k: the quadrant's pixels stop early, each at a depth of its own, and the other quadrants run to the end.
+    wall=k: the last 3 entries become near-opaque Gaussians (opacity 0.999, centred outside the image, wide enough
+    that 0.999 G >= 0.99 -- their alpha is the clamp's 0.99 -- at every pixel) between stack entries k - 1 and k: every
+    pixel blends the first and stops at the second, so every tile's n_eff is k + 1 under a list of n.
+    Returns (model, cam) on the CPU; what a case must exercise is asserted by tests/blend_reference.py."""
+    from gslm.model import GaussianModel, RGB2SH, inverse_sigmoid
+    cam = orbit_cameras(1, W, H, seed=1)[0]
+    cam.original_image = torch.rand(3, H, W, generator=torch.Generator().manual_seed(8))
+    g = torch.Generator().manual_seed(1000 + seed)
+    fx = W / (2.0 * math.tan(cam.FoVx * 0.5))
+    n_extra = 27 if blobs is not None else (3 if wall is not None else 0)
+    assert blobs is None or wall is None
+    ns = n - n_extra
+    assert ns >= 1
+    z = STACK_Z0 + STACK_DZ * torch.arange(ns, dtype=torch.float64)
+    cx, cy = math.floor(0.5 * (W - 1)) + 0.5, math.floor(0.5 * (H - 1)) + 0.5
+    px = cx + 2 * jitter * (torch.rand(ns, generator=g) - 0.5)
+    py = cy + 2 * jitter * (torch.rand(ns, generator=g) - 0.5)
+    s_world = (sigma_px / fx) * z.float()
+    scaling = torch.log(s_world[:, None] * (0.9 + 0.2 * torch.rand(ns, 3, generator=g)) * torch.tensor(ANISOTROPY))
+    rotation = torch.randn(ns, 4, generator=g)
+    opacity = a * (0.75 + 0.5 * torch.rand(ns, 1, generator=g))
+    dc = RGB2SH(torch.rand(ns, 1, 3, generator=g))
+    rest = 0.05 * torch.randn(ns, 3, 3, generator=g)
+    if n_extra:
+        ge = torch.Generator().manual_seed(2000 + seed)
+        if blobs is not None:
+            q, k = blobs
+            assert 1 <= k <= ns
+            gx, gy = torch.meshgrid(torch.tensor(BLOB_GRID), torch.tensor(BLOB_GRID), indexing="ij")
+            ex = (8.0 * (q & 1) + gx.reshape(-1)).repeat(3) + 0.3 * (torch.rand(27, generator=ge) - 0.5)
+            ey = (8.0 * (q >> 1) + gy.reshape(-1)).repeat(3) + 0.3 * (torch.rand(27, generator=ge) - 0.5)
+            e_sigma, e_op = torch.full((27,), 2.5), torch.full((27, 1), 0.97)
+        else:
+            k = wall
+            assert 1 <= k <= ns
+            # outside the image (just inside the tan-FoV clamp's 0.15 W, 0.15 H), |exponent| from WALL_POWER_MIN at the
+            # nearest pixel to 66 times that at the farthest (measured 1.2e-4 .. 0.0078): below -ln(0.99 / 0.999) = 0.00905, where
+            # the alpha would leave the 0.99 clamp
+            ex = -0.145 * W + 0.1 * (torch.rand(3, generator=ge) - 0.5)
+            ey = -0.145 * H + 0.1 * (torch.rand(3, generator=ge) - 0.5)
+            e_sigma = torch.full((3,), math.hypot(0.145 * W - 0.05, 0.145 * H - 0.05) / math.sqrt(2 * WALL_POWER_MIN))
+            e_op = torch.full((3, 1), 0.999)
+        ez = STACK_Z0 + STACK_DZ * (k - 1 + (1.0 + torch.arange(n_extra, dtype=torch.float64)) / (n_extra + 1))
+        z, px, py = torch.cat([z, ez]), torch.cat([px, ex]), torch.cat([py, ey])
+        scaling = torch.cat([scaling, torch.log((e_sigma / fx) * ez.float())[:, None].repeat(1, 3)])
+        rotation = torch.cat([rotation, torch.randn(n_extra, 4, generator=ge)])
+        opacity = torch.cat([opacity, e_op])
+        dc = torch.cat([dc, RGB2SH(torch.rand(n_extra, 1, 3, generator=ge))])
+        rest = torch.cat([rest, 0.05 * torch.randn(n_extra, 3, 3, generator=ge)])
+    m = GaussianModel(1)
+    m.set_params(_world_from_pixel(cam, px, py, z), dc, rest, scaling, rotation, inverse_sigmoid(opacity),
+                 torch.eye(3, 4)[None])
+    m.active_sh_degree = 1
+    return m, cam
+
+
 def to_float64(model, cams):
     """Deep copies of the model and cameras on the CPU in float64 (the oracle then runs in double)."""
     import copy
