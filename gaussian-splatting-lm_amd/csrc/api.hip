@@ -1039,6 +1039,54 @@ int gslm_gather_screen(const gslm_view* views, int32_t nviews, const gslm_gaussi
   return GSLM_OK;
 }
 
+int gslm_gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t nviews, const gslm_gaussians* gi,
+                      const gslm_grads* vin, const gslm_grads* y, const gslm_matvec_opts* opts, void* stream) {
+  if (!views || !ws || nviews < 1 || nviews > MAX_SCREEN_VIEWS || !gi || !vin || !y) {
+    set_error("gather_views: NULL argument or nviews outside 1..16");
+    return GSLM_ERR_INVALID;
+  }
+  ViewK vk[MAX_SCREEN_VIEWS];
+  GeomBufs gbs[MAX_SCREEN_VIEWS];
+  ScratchBufs sbs[MAX_SCREEN_VIEWS];
+  int64_t nr[MAX_SCREEN_VIEWS];
+  GaussK g;
+  int st;
+  for (int b = 0; b < nviews; ++b) {
+    if ((st = make_view(&views[b], gi->max_coeffs, &vk[b]))) return st;
+    vk[b].stop = opts ? opts->cg_ctl : nullptr;  // a stopped solve's gather returns at once
+  }
+  if ((st = make_gauss(gi, &vk[0], &g, false))) return st;
+  if (!g.raw) { set_error("gather_views: gaussians must be the raw GaussianModel leaves (raw = 1)"); return GSLM_ERR_INVALID; }
+  for (int b = 0; b < nviews; ++b) {
+    nr[b] = ws[b].num_rendered;
+    if (nr[b] < 0 || (nr[b] > 0 && g.P > 0 && (!ws[b].geom || !ws[b].scratch))) {
+      set_error("gather_views: negative num_rendered or a NULL workspace of a view that rendered");
+      return GSLM_ERR_INVALID;
+    }
+    if (nr[b] == 0) continue;  // nothing rendered: no row map exists, the workspaces are not read
+    if (ws[b].scratch_bytes < gslm_scratch_bytes(g.P, nr[b])) {
+      set_error("gather_views: scratch workspace too small");
+      return GSLM_ERR_CAPACITY;
+    }
+    geom_layout(g.P, const_cast<void*>(ws[b].geom), &gbs[b]);
+    scratch_layout(g.P, nr[b], const_cast<void*>(ws[b].scratch), &sbs[b]);
+  }
+  const int32_t stages = (opts && opts->stages) ? opts->stages : GSLM_STAGE_ALL;
+  const double* damp7 = opts ? opts->damp7 : nullptr;
+  double* dot_out = opts ? opts->dot_vy : nullptr;
+  if (dot_out && (!opts->dot_scratch || opts->dot_scratch_bytes < gslm_dot_scratch_bytes(g.P))) {
+    set_error("gather_views: dot scratch too small");
+    return GSLM_ERR_CAPACITY;
+  }
+  double* part = dot_out ? (double*)opts->dot_scratch : nullptr;
+  RestK rc;
+  if ((st = rest_opts("gather_views", opts, nviews, &rc))) return st;
+  if ((st = launch_gather_views(vk, gbs, sbs, nr, nviews, g, make_gradk(y), make_gradk(vin), damp7,
+                                (stages & GSLM_STAGE_OVERWRITE) != 0, part, dot_out, (hipStream_t)stream, rc)))
+    return st;
+  return GSLM_OK;
+}
+
 int gslm_view_flags(const void* geom, int64_t P, uint32_t* out, void* stream) {
   if (P < 0 || (P > 0 && (!geom || !out))) { set_error("view_flags: NULL geom / out"); return GSLM_ERR_INVALID; }
   GeomBufs gb;

@@ -1,0 +1,157 @@
+// gather_views.hip -- the per-Gaussian side of the single-process multi-view LM product (gslm_gather_views,
+// gslm.lm.BatchedLMProblem): one pass over the Gaussians sums every view's head rows and applies every view's
+// chain, where the per-view loop runs one k_gather_lm per view (each re-reading and re-writing the whole y) and
+// the exchange's form runs one k_rowsum_screen per view into a [P][8] table that k_gather_screen reads back.
+//   y = [y +] [D v +] sum_b C_b^T (sum of Gaussian i's head rows in view b),   <v, y> partials
+// Same row sums (block_sum_rows<2> over the same 256-Gaussian partition), same chain and the same accumulation
+// order as k_rowsum_screen x V + k_gather_screen, so the results are those kernels' bit for bit.
+#include "gslm_gather.hpp"
+
+namespace gslm {
+
+// Every view's geometry workspace has the layout of the same P (geom_layout), so goff and clampw lie at one
+// offset from tiles in all of them; a view's hscan lies hoff float4 past its rows (scratch_layout).  rows NULL:
+// the view rendered nothing (no row map exists), it is skipped.
+struct ViewWsK {
+  const uint32_t* tiles[MAX_SCREEN_VIEWS];
+  const float4* rows[MAX_SCREEN_VIEWS];
+  uint32_t hoff[MAX_SCREEN_VIEWS];
+  int32_t goff_off, clamp_off;  // in words, from tiles
+};
+static_assert(sizeof(ViewsK) + sizeof(ViewWsK) + sizeof(GaussK) + sizeof(FlatK) + sizeof(RestK) <= 4096,
+              "k_gather_views: kernel arguments past 4 KB");
+
+template <bool COORDS>
+__global__ __launch_bounds__(256) void k_gather_views(ViewsK vs, ViewWsK ws, GaussK g, FlatK o, RestK rc) {
+  extern __shared__ __attribute__((aligned(16))) float s_rest[];  // the views' row chunks, then the epilogue's stage
+  __shared__ double s_dot[4];
+  if (cg_stopped(vs.v[0])) return;  // a stopped solve (gslm_matvec_opts.cg_ctl): block-uniform, before any barrier
+  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x;
+  const int64_t i = i0 + threadIdx.x;
+  const int64_t il = i0 + min((int64_t)blockDim.x, g.P - i0) - 1;  // the block's last Gaussian
+  ChainOut acc;
+  acc.dop = 0.f;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) { acc.dscale[k] = 0.f; acc.dmean[k] = 0.f; }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) acc.drot[k] = 0.f;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) acc.dsh[k][0] = acc.dsh[k][1] = acc.dsh[k][2] = 0.f;
+#pragma unroll 1
+  for (int b = 0; b < vs.n; ++b) {
+    const float4* __restrict__ rows = ws.rows[b];
+    if (!rows) continue;  // an empty view: a kernel argument, so the whole block skips it (no barrier is missed)
+    const uint32_t* __restrict__ tiles = ws.tiles[b];
+    const uint32_t* __restrict__ goff = tiles + ws.goff_off;
+    const uint32_t* __restrict__ hscan = reinterpret_cast<const uint32_t*>(rows + ws.hoff[b]);
+    // the block's contiguous head-row range of this view and this Gaussian's part of it (k_rowsum_screen); every
+    // thread runs the row sums -- they hold barriers -- also past P and for a Gaussian the view does not see
+    const uint32_t n = i < g.P ? tiles[i] : 0u;
+    const uint32_t R0 = hscan[goff[i0]], R1 = hscan[goff[il] + tiles[il]];
+    const uint32_t h0 = i < g.P ? hscan[goff[i]] : R1, h1 = i < g.P ? hscan[goff[i] + n] : R1;
+    float G2[NV];
+    block_sum_rows<2>(rows, R0, R1, h0, h1 - h0, reinterpret_cast<float4*>(s_rest), G2);
+    if (!n) continue;
+    ChainOut co;
+    chain_vjp<true>(vs.v[b], g, i, true, (tiles + ws.clamp_off)[i] & 7u, G2, false, co);
+    acc.dop += co.dop;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) acc.dscale[k] += co.dscale[k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) acc.drot[k] += co.drot[k];
+    if constexpr (COORDS) {
+      // SH-rest coordinates (k_gather_screen<true>): view b is column view_base + b of R
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) acc.dsh[0][ch] += co.dsh[0][ch];
+      const int col = rc.view_base + b;
+      const float* Rc = rc.R + i * rest_basis_floats(rc.V) + rest_basis_floats(col);
+#pragma unroll
+      for (int j = 0; j < MAX_REST_VIEWS; ++j)
+        if (j <= col) {
+          const float r = Rc[j];
+#pragma unroll
+          for (int ch = 0; ch < 3; ++ch) acc.dsh[1 + j][ch] += r * co.dres[ch];
+        }
+    } else {
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        acc.dsh[k][0] += co.dsh[k][0];
+        acc.dsh[k][1] += co.dsh[k][1];
+        acc.dsh[k][2] += co.dsh[k][2];
+      }
+    }
+  }
+  lm_epilogue<false>(g.M, g, acc, o, s_rest, s_dot);
+}
+
+// <v, y> from the blocks' partials: k_dot_final's sum (cg.hip), except that a stopped solve -- whose gather wrote no
+// partials -- leaves the dot as it is
+__global__ __launch_bounds__(256) void k_dot_final_views(const double* __restrict__ part, int np,
+                                                         double* __restrict__ out, const double* __restrict__ ctl) {
+  __shared__ double s[4];
+  if (ctl != nullptr && *ctl != 0.0) return;
+  double x = strided_sum_in_order(part, np);
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+  if (lane == 0) s[w] = x;
+  __syncthreads();
+  if (tid == 0) *out = ((s[0] + s[1]) + s[2]) + s[3];
+}
+
+int launch_gather_views(const ViewK* views, const GeomBufs* gbs, const ScratchBufs* sbs, const int64_t* nr,
+                        int nviews, const GaussK& g, const GradK& y, const GradK& vin, const double* damp7,
+                        bool overwrite, double* dot_part, double* dot_out, hipStream_t s, const RestK& rc) {
+  if (g.P == 0) {
+    if (dot_out) {  // an empty sum
+      hipLaunchKernelGGL(k_dot_final_views, dim3(1), dim3(256), 0, s, dot_part, 0, dot_out, views[0].stop);
+      GSLM_LAUNCH_CHECK();
+    }
+    return GSLM_OK;
+  }
+  FlatK o;
+  const int st = make_flatk(g, y, vin, damp7, overwrite, dot_part, &o, false, rc.R ? rc.V : 0);
+  if (st) return st;
+  if (nviews < 1 || nviews > MAX_SCREEN_VIEWS) {
+    set_error("gather_views: 1..16 views per call");
+    return GSLM_ERR_INVALID;
+  }
+  ViewsK vs;
+  ViewWsK ws{};
+  vs.n = nviews;
+  for (int b = 0; b < nviews; ++b) {
+    vs.v[b] = views[b];
+    if (nr[b] <= 0) continue;  // rows stays NULL: skipped
+    // (the geometry layout depends on P only: any view's offsets are every view's)
+    ws.goff_off = (int32_t)(gbs[b].goff - gbs[b].tiles);
+    ws.clamp_off = (int32_t)(gbs[b].clampw - gbs[b].tiles);
+    const size_t hbytes = (size_t)(reinterpret_cast<const char*>(sbs[b].hscan) -
+                                   reinterpret_cast<const char*>(sbs[b].contrib));
+    if (hbytes % sizeof(float4) != 0 || hbytes / sizeof(float4) > 0xFFFFFFFFull) {
+      set_error("gather_views: num_rendered too large for the row map offset");
+      return GSLM_ERR_INVALID;
+    }
+    ws.tiles[b] = gbs[b].tiles;
+    ws.rows[b] = sbs[b].contrib;
+    ws.hoff[b] = (uint32_t)(hbytes / sizeof(float4));
+  }
+  const unsigned nb = (unsigned)((g.P + 255) / 256);
+  const size_t chunk_lds = (size_t)GATHER_CHUNK * 2 * sizeof(float4);
+  if (o.rest_V) {
+    const size_t stage = (size_t)256 * 3 * o.rest_V * sizeof(float);
+    hipLaunchKernelGGL(k_gather_views<true>, dim3(nb), dim3(256), (stage > chunk_lds ? stage : chunk_lds) + 16, s, vs,
+                       ws, g, o, rc);
+  } else {
+    const size_t stage = sh_stage_floats<false>(g.M) * sizeof(float);
+    hipLaunchKernelGGL(k_gather_views<false>, dim3(nb), dim3(256), (stage > chunk_lds ? stage : chunk_lds) + 16, s,
+                       vs, ws, g, o, rc);
+  }
+  GSLM_LAUNCH_CHECK();
+  if (dot_out) {
+    hipLaunchKernelGGL(k_dot_final_views, dim3(1), dim3(256), 0, s, dot_part, (int)nb, dot_out, views[0].stop);
+    GSLM_LAUNCH_CHECK();
+  }
+  return GSLM_OK;
+}
+
+}  // namespace gslm

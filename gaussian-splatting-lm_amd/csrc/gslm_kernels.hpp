@@ -605,6 +605,12 @@ struct ViewsK {
 int launch_gather_screen(const ViewK* views, int nviews, const GaussK& g, const float* screen, int64_t sstride,
                          const GradK& y, const GradK& vin, const double* damp7, bool overwrite, double* dot_part,
                          hipStream_t s, const RestK& rc = RestK{});
+// every view's head rows (the LM row maps of gbs / sbs; nr[b] <= 0: view b rendered nothing, its buffers are not read)
+// summed and chained per Gaussian in one pass (gslm_gather_views, gather_views.hip); dot_out (or NULL) = the sum of
+// the dot_part partials, left alone by a stopped solve
+int launch_gather_views(const ViewK* views, const GeomBufs* gbs, const ScratchBufs* sbs, const int64_t* nr,
+                        int nviews, const GaussK& g, const GradK& y, const GradK& vin, const double* damp7,
+                        bool overwrite, double* dot_part, double* dot_out, hipStream_t s, const RestK& rc = RestK{});
 int launch_rest_basis(const ViewK* views, int nviews, const GaussK& g, float* R, hipStream_t s);
 int launch_rest_coords(const ViewK* views, int nviews, const GaussK& g, const float* R, int mode, const float* in,
                        int64_t in_stride, float* out, int64_t out_stride, hipStream_t s);

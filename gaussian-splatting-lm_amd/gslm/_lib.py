@@ -67,6 +67,14 @@ class GslmMatvecOpts(ctypes.Structure):
     ]
 
 
+class GslmViewWs(ctypes.Structure):
+    """gslm_view_ws: one view's workspaces for gslm_gather_views."""
+    _fields_ = [
+        ("geom", ctypes.c_void_p), ("scratch", ctypes.c_void_p), ("scratch_bytes", ctypes.c_size_t),
+        ("num_rendered", ctypes.c_int64),
+    ]
+
+
 class GslmAdamGroup(ctypes.Structure):
     _fields_ = [
         ("param", ctypes.c_void_p), ("grad", ctypes.c_void_p), ("exp_avg", ctypes.c_void_p),
@@ -183,6 +191,9 @@ EXPORTS = {
     "gslm_gather_screen": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int32, ctypes.POINTER(GslmGaussians),
                                           ctypes.c_void_p, ctypes.POINTER(GslmGrads), ctypes.POINTER(GslmGrads),
                                           ctypes.c_void_p, ctypes.c_void_p]),
+    "gslm_gather_views": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.POINTER(GslmViewWs), ctypes.c_int32,
+                                         ctypes.POINTER(GslmGaussians), ctypes.POINTER(GslmGrads),
+                                         ctypes.POINTER(GslmGrads), ctypes.c_void_p, ctypes.c_void_p]),
     "gslm_view_flags": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
     "gslm_tangent_views": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int32, ctypes.POINTER(GslmGaussians),
                                           ctypes.POINTER(GslmGrads), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,

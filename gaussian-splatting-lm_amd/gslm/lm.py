@@ -661,6 +661,231 @@ class LMProblem:
         return torch.zeros(self.layout.numel, dtype=torch.float32, device=self.device)
 
 
+class BatchedLMProblem(LMProblem):
+    """LMProblem over several views with one batched pass per product and per J^T b on one GPU (the reference's
+    view batch, train_jvp.py --num_images): where LMProblem runs the whole fused product once per view -- the
+    per-Gaussian tangent kernel over all P, and a gather that re-reads and re-writes all of y, V times -- this runs
+      gslm_tangent_views   every view's tangent records in one pass over theta and p (per 16 views), with the fused
+                           direction update and deferred x update of cgls_fused;
+      RENDER (trec_in)     each view's fused J v -> J^T tile pass into its own head rows;
+      gslm_gather_views    every view's row sums and chain per Gaussian, D v and <v, y>, y written once (per 16 views).
+    With V <= GSLM_MAX_REST_VIEWS views (and 3 V < 3 (K - 1)) the SH-rest group of every vector is carried in the 3 V
+    gslm_rest_basis coordinates of the views' span (GSLM_SHARD_REST=full keeps the reference's layout); `expand` /
+    `project` convert to and from `full_layout`.  The forwards, residuals and the loss are LMProblem's own.
+    mask_xyz=True and the disable_ssim residual only."""
+
+    CHUNK = 16  # views per gslm_tangent_views / gslm_gather_views call
+    STAGES = ("tangent_views", "tile_passes", "gather_views")
+    _events = None  # stage_times: HIP events recorded between the product's stages
+
+    def __init__(self, model, cams, bg, gts=None, alpha_masks=None, mask_xyz=True, damp=None, device="cuda",
+                 ssim=False, lambda_dssim=0.2, sh_projection=False):
+        if not mask_xyz:
+            raise ValueError("BatchedLMProblem runs on the LM rows (mask_xyz=True, train_jvp.py:221-227)")
+        if ssim:
+            raise ValueError("BatchedLMProblem runs the disable_ssim residual")
+        if len(cams) < 1:
+            raise ValueError("BatchedLMProblem needs at least one view")
+        if sh_projection not in (False, None, "auto"):
+            raise ValueError("sh_projection is LMProblem's single-view mode; the batch carries SH-rest coordinates")
+        super().__init__(model, cams, bg, gts=gts, alpha_masks=alpha_masks, mask_xyz=True, damp=damp, device=device,
+                         ssim=False, lambda_dssim=lambda_dssim, sh_projection=False)
+        full = self.full_layout
+        P, K, V = full.P, full.K, len(cams)
+        self.rest_views = V if (K > 1 and V <= _lib.GSLM_MAX_REST_VIEWS and 3 * V < 3 * (K - 1)
+                                and os.environ.get("GSLM_SHARD_REST", "coords") != "full") else 0
+        if self.rest_views:
+            self.layout = ParamLayout(P, K, full.n_exposure, rest_views=self.rest_views)
+            self._bounds, self._damps = self.layout.group_damp_arrays(self.damp)
+        self._views_arr = (_lib.GslmView * V)(*[vr.view for vr in self.views])
+        # allocated once: every view's visibility words and tangent records, the SH-rest factors
+        self._flags = torch.zeros(V, max(P, 1), dtype=torch.int32, device=device)
+        self._trec = torch.zeros(V, max(P, 1), 8, dtype=torch.float32, device=device)
+        rv = self.rest_views
+        self._rest_n = P * rv * (rv + 1) // 2  # floats gslm_rest_basis writes
+        self._rest_R = torch.zeros((self._rest_n + 255) // 256 * 256, dtype=torch.float32,
+                                   device=device) if rv else None
+        self._rest_ok = False
+
+    def active_view(self):
+        return None  # (a union list over several views is not built: cgls_fused takes its ordinary loop)
+
+    def _mark(self, k):
+        if self._events is not None:
+            self._events[k].record()
+
+    def stage_times(self, v, reps=10):
+        """Per-stage time of a product of direction v (ms, mean over `reps`): HIP events on the product's stream
+        between its three stages (as GaussianShardedOperator.stage_times)."""
+        y = self.zeros()
+        evs = []
+        for _ in range(reps):
+            self._events = [torch.cuda.Event(enable_timing=True) for _ in range(len(self.STAGES) + 1)]
+            self.matvec_dot(v, y, None)
+            evs.append(self._events)
+            self._events = None
+        torch.cuda.synchronize()
+        out = {name: sum(e[k].elapsed_time(e[k + 1]) for e in evs) / reps for k, name in enumerate(self.STAGES)}
+        out["total"] = sum(e[0].elapsed_time(e[-1]) for e in evs) / reps
+        return out
+
+    def _view_ptr(self, c0):
+        return ctypes.cast(ctypes.byref(self._views_arr, c0 * ctypes.sizeof(_lib.GslmView)),
+                           ctypes.POINTER(_lib.GslmView))
+
+    def evaluate(self):
+        """LMProblem.evaluate (the same forwards and residual epilogues: the same loss bits); then, once per geometry,
+        every view's visibility words; the SH-rest factors of the new geometry are recomputed on first use."""
+        loss = super().evaluate()
+        P = self.layout.P
+        for b, vr in enumerate(self.views):
+            check(lib.gslm_view_flags(vr.geom.data_ptr(), P, self._flags[b].data_ptr(), self.stream),
+                  "gslm_view_flags")
+        self._rest_ok = False
+        return loss
+
+    def rest_basis(self):
+        """gslm_rest_basis of the batch's views on the current geometry (None in the full layout)."""
+        if not self.rest_views:
+            return None
+        if not self._rest_ok:
+            g = raw_gaussians(self.model)
+            check(lib.gslm_rest_basis(self._views_arr, self.rest_views, ctypes.byref(g), self._rest_R.data_ptr(),
+                                      self.stream), "gslm_rest_basis")
+            self._rest_ok = True
+        return self._rest_R
+
+    # -------------------------------------------------------------- SH-rest coordinates
+    def _rest_convert(self, mode, src, dst, src_layout, dst_layout):
+        """gslm_rest_coords between the rest groups of two flat vectors (mode 0 expand, 1 project)."""
+        g = raw_gaussians(self.model)
+        a0 = src_layout.offsets["features_rest"][0]
+        b0 = dst_layout.offsets["features_rest"][0]
+        check(lib.gslm_rest_coords(self._views_arr, self.rest_views, ctypes.byref(g), self.rest_basis().data_ptr(),
+                                   mode, src.data_ptr() + 4 * a0, 3 * src_layout.rest_rows, dst.data_ptr() + 4 * b0,
+                                   3 * dst_layout.rest_rows, self.stream), "gslm_rest_coords")
+
+    def expand(self, x, out=None):
+        """A vector of this problem's layout in the reference's (full_layout); x itself in the full layout."""
+        if not self.rest_views:
+            return x
+        out = torch.empty(self.full_layout.numel, dtype=torch.float32, device=x.device) if out is None else out
+        self._copy_other_groups(x, out, self.layout, self.full_layout)
+        self._rest_convert(0, x, out, self.layout, self.full_layout)
+        return out
+
+    def project(self, x_full, out=None):
+        """full_layout -> this problem's layout (the orthogonal projection onto the views' SH-rest span)."""
+        if not self.rest_views:
+            return x_full if out is None else out.copy_(x_full)
+        out = torch.empty(self.layout.numel, dtype=torch.float32, device=x_full.device) if out is None else out
+        self._copy_other_groups(x_full, out, self.full_layout, self.layout)
+        self._rest_convert(1, x_full, out, self.full_layout, self.layout)
+        return out
+
+    # -------------------------------------------------------------- the batched passes
+    def _gather(self, g, vs, ys, damp, dot_out, cg_ctl):
+        """gslm_gather_views over the views' head rows: y = [D v +] sum_b C_b^T rows_b, <v, y> with the last chunk."""
+        V = len(self.views)
+        R = self.rest_basis()
+        for c0 in range(0, V, self.CHUNK):
+            c1 = min(V, c0 + self.CHUNK)
+            opts = _lib.GslmMatvecOpts()
+            opts.stages = STAGE_ALL | (STAGE_OVERWRITE if c0 == 0 else 0)
+            opts.damp7 = self._damps if (damp and c0 == 0) else None
+            opts.cg_ctl = cg_ctl
+            if R is not None:
+                opts.rest_basis, opts.rest_views, opts.view_base = R.data_ptr(), self.rest_views, c0
+            if dot_out is not None and c1 == V:
+                opts.dot_vy = dot_out
+                opts.dot_scratch = self.dot_scratch.data_ptr()
+                opts.dot_scratch_bytes = self.dot_scratch.numel() * 8
+            ws = (_lib.GslmViewWs * (c1 - c0))()
+            for k, vr in enumerate(self.views[c0:c1]):
+                ws[k].geom, ws[k].scratch = vr.geom.data_ptr(), vr.scratch.data_ptr()
+                ws[k].scratch_bytes, ws[k].num_rendered = vr.scratch.numel(), vr.N
+            check(lib.gslm_gather_views(self._view_ptr(c0), ws, c1 - c0, ctypes.byref(g), ctypes.byref(vs),
+                                        ctypes.byref(ys), ctypes.byref(opts), self.stream), "gslm_gather_views")
+
+    def rhs(self, out, fused=True):
+        """out = J^T b in this problem's layout (xyz, exposure zeroed): per view the seeded back-to-front pass into
+        its head rows, then one gslm_gather_views -- in coordinates it writes the coordinates of J^T b directly."""
+        g = raw_gaussians(self.model)
+        ys = self.layout.grads_struct(out)
+        for b, vr in enumerate(self.views):
+            opts = _lib.GslmMatvecOpts()
+            opts.stages = 2  # RENDER, seeded
+            opts.flags = MV_TAIL_CLEAN if vr.tail_clean else 0
+            opts.pixel_seed = self.seeds[b].data_ptr()
+            check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(ys),
+                                          self.seeds[b].data_ptr(), 1, vr.geom.data_ptr(), vr.binning.data_ptr(),
+                                          vr.N, vr.image.data_ptr(), vr.scratch.data_ptr(), vr.scratch.numel(),
+                                          ctypes.byref(ys), ctypes.byref(opts), self.stream),
+                  "gslm_matvec_view_ex(seed)")
+            vr.tail_clean = True
+        self._gather(g, ys, ys, False, None, None)
+        e0, e1 = self.layout.offsets["exposure"]
+        out[e0:e1].zero_()
+        return self._mark_rhs(out)
+
+    def matvec_dot(self, v, y, dot_out, pre=None, exposure_zero=False, cg_ctl=None):
+        """LMProblem.matvec_dot; <v, y> is fused into the gather for any number of views (True with dot_out)."""
+        self.local_normal_matvec(v, y, damp=True, dot_out=dot_out, pre=pre, exposure_zero=exposure_zero,
+                                 cg_ctl=cg_ctl)
+        return dot_out is not None
+
+    def local_normal_matvec(self, v, y, damp=False, dot_out=None, pre=None, exposure_zero=False, cg_ctl=None):
+        """y = [D v +] sum_b 2 J_b^T W_b J_b v (overwrites y); pre, exposure_zero, cg_ctl: see LMProblem.matvec_dot."""
+        g = raw_gaussians(self.model)
+        vs = self.layout.grads_struct(v)
+        ys = self.layout.grads_struct(y)
+        V, P = len(self.views), self._flags.shape[1]
+        R = self.rest_basis()
+        keep = []
+        self._mark(0)
+        # 1. every view's tangent records, one pass over the Gaussians per chunk (the direction update with the first)
+        for c0 in range(0, V, self.CHUNK):
+            c1 = min(V, c0 + self.CHUNK)
+            opts = None
+            if (pre is not None and c0 == 0) or R is not None or cg_ctl is not None:
+                opts = _lib.GslmMatvecOpts()
+                opts.cg_ctl = cg_ctl
+                if pre is not None and c0 == 0:
+                    keep.append(self._pre_opts(opts, v, pre))
+                if R is not None:
+                    opts.rest_basis, opts.rest_views, opts.view_base = R.data_ptr(), self.rest_views, c0
+            check(lib.gslm_tangent_views(self._view_ptr(c0), c1 - c0, ctypes.byref(g), ctypes.byref(vs), 1,
+                                         self._flags.data_ptr() + 4 * c0 * P, P,
+                                         self._trec.data_ptr() + 32 * c0 * P, P,
+                                         None if opts is None else ctypes.byref(opts), self.stream),
+                  "gslm_tangent_views")
+        self._mark(1)
+        # 2. each view's tile pass from its slice of the table, into its own head rows
+        for b, vr in enumerate(self.views):
+            opts = _lib.GslmMatvecOpts()
+            opts.stages = 2  # RENDER
+            opts.flags = MV_TAIL_CLEAN if vr.tail_clean else 0
+            opts.trec_in = self._trec[b].data_ptr()
+            opts.cg_ctl = cg_ctl
+            check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(vs),
+                                          self.weights[b].data_ptr(), 1, vr.geom.data_ptr(), vr.binning.data_ptr(),
+                                          vr.N, vr.image.data_ptr(), vr.scratch.data_ptr(), vr.scratch.numel(),
+                                          ctypes.byref(vs), ctypes.byref(opts), self.stream), "gslm_matvec_view_ex")
+            vr.tail_clean = True
+        self._mark(2)
+        # 3. every view's row sums and chain per Gaussian, y written once per chunk
+        self._gather(g, vs, ys, damp, dot_out, cg_ctl)
+        self._mark(3)
+        e0, e1 = self.layout.offsets["exposure"]
+        if exposure_zero:
+            pass  # y[e0:e1] = D v[e0:e1] = 0 already (LMProblem.matvec_dot)
+        elif damp:
+            torch.mul(v[e0:e1], float(self._damps[6]), out=y[e0:e1])  # J has no exposure column
+        else:
+            y[e0:e1].zero_()
+        return y
+
+
 class NonFiniteError(AssertionError):
     """A NaN or Inf reached the normal equations.  The reference's only failure detection on the LM path is
     matvec_T's `assert not torch.isnan(self.gaussians._<group>.grad).any(), "NaN detected in gaussians._<group>.grad"`
@@ -1370,7 +1595,8 @@ def clear_val_cache():
 
 def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, mask_xyz=True, check_every=True,
             verbose=False, device="cuda", sh_projection="auto", recursion="fused", exchange="auto", group=None,
-            val_batch=8, timing=False, backend=None, line_search="union", val_at_start=False, cache_val=True):
+            val_batch=8, timing=False, backend=None, line_search="union", val_at_start=False, cache_val=True,
+            multiview="loop"):
     """One LM step of train_jvp.py:237-289: loss, CGLS on the normal equations, backtracking line search.
 
     Single process: LMProblem over `cams` (with one training view the SH-rest group of the CG vectors is carried
@@ -1391,6 +1617,10 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     (one more evaluation, outside the reference's algorithm: it shows whether the step descends).  cache_val: keep the
     validation evaluator for the next LM step (its workspaces and cached depth orders; clear_val_cache() releases it;
     the views are rebuilt from the cameras every step, so a moved camera is rendered at its new pose).
+    multiview: "loop" (LMProblem: the whole fused product once per training view) or "batched" (BatchedLMProblem: one
+    tangent pass and one gather over the Gaussians for all the views, the SH-rest group in the views' coordinates;
+    single process, recursion="fused", mask_xyz=True -- anything else raises ValueError; with one training view the
+    existing path runs).  The step comes back in the reference's layout either way.
     backend: (problem_cls, evaluator_cls, solver) replacing (LMProblem, LossEvaluator, cgls_fused) -- the CPU
     multi-process tests run this same driver, sharding and reductions on the oracle restatement."""
     import time
@@ -1398,6 +1628,14 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     rank, n = world()
     sharded = collectives_on(n)
     problem_cls, evaluator_cls, solver = backend if backend is not None else (LMProblem, LossEvaluator, cgls_fused)
+    if multiview not in ("loop", "batched"):
+        raise ValueError(f"multiview must be 'loop' or 'batched', got {multiview!r}")
+    if multiview == "batched":
+        if sharded or backend is not None or recursion != "fused" or not mask_xyz:
+            raise ValueError("multiview='batched' is the single-process HIP problem with recursion='fused' and "
+                             "mask_xyz=True")
+        if len(cams) > 1:
+            problem_cls = BatchedLMProblem
     t = {}
     clock = [time.perf_counter()]
 

@@ -387,6 +387,29 @@ int gslm_active_unpack(const float* src, float* dst, const int32_t* active_ids, 
 int gslm_gather_screen(const gslm_view* views, int32_t nviews, const gslm_gaussians* g, const float* screen,
                        const gslm_grads* v, const gslm_grads* y, const gslm_matvec_opts* opts, void* stream);
 
+/* ---- single-process multi-view product (additive entry point, still ABI 9; gslm.lm.BatchedLMProblem) ----
+ * gslm_gather_screen with the views' row sums fused in: instead of one SCREEN stage per view into a [P][8] table,
+ * gslm_gather_views reads every view's head rows where the last RENDER stage of that view left them (the fused
+ * product, the pixel_seed pass or the trec_in form), addressed through that view's LM row map -- so ws[b] must be
+ * the geometry and scratch of a view for which GSLM_MV_TAIL_CLEAN may be passed -- and writes
+ *   y = [y +] [D v +] sum_b C_b^T (sum of the head rows of Gaussian i in view b)   (views summed in index order)
+ * in one pass over the Gaussians: V row sums, V chains, one read and one write of y.  xyz-masked form only: no view
+ * adds to y.xyz (with OVERWRITE it is written as the D v term alone, as gslm_gather_screen does).  opts as gslm_gather_screen: the OVERWRITE bit of stages,
+ * damp7, dot_vy / dot_scratch, cg_ctl (a stopped solve leaves y and *dot_vy as they are) and rest_basis / rest_views / view_base (y's SH-rest group then holds the
+ * gslm_rest_basis coordinates).  A view with num_rendered == 0 contributes nothing and its workspaces are not
+ * read (no row map exists for it).  nviews 1..16 per call (accumulate further calls).  GSLM_ERR_INVALID: NULL
+ * arguments, nviews outside 1..16, non-raw Gaussians, group strides that do not match the layout, rest_basis with
+ * rest_views outside 1..GSLM_MAX_REST_VIEWS; GSLM_ERR_CAPACITY: a scratch below gslm_scratch_bytes(P,
+ * num_rendered) or a dot scratch below gslm_dot_scratch_bytes(P).  Nothing is launched on an error. */
+typedef struct gslm_view_ws {
+  const void* geom;        /* the view's geometry workspace */
+  const void* scratch;     /* the view's matvec scratch: its LM row map and head rows */
+  size_t scratch_bytes;
+  int64_t num_rendered;
+} gslm_view_ws;
+int gslm_gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t nviews, const gslm_gaussians* g,
+                      const gslm_grads* v, const gslm_grads* y, const gslm_matvec_opts* opts, void* stream);
+
 /* ---- Gaussian-sharded exchange (multi-GPU LM product; gslm.parallel.GaussianShardedOperator, exchange
  * "gaussian", the default of gslm.parallel.ShardedLMProblem when every rank renders the same number of views) ----
  * Rank r owns Gaussians [r S, (r + 1) S) of every CG vector and the vector algebra on them.  Per product:
