@@ -734,6 +734,8 @@ static int build_xpby(const gslm_matvec_opts* opts, const gslm_grads* vin, int R
   return GSLM_OK;
 }
 
+static const uint32_t* active_params_bind(const void* block, int64_t na, GaussK* g);
+
 // gslm_matvec_view_ex (na < 0) and gslm_matvec_view_active (na >= 0: the groups of vin, y and the fused direction
 // update hold the na Gaussians ids[0 .. na) only)
 static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gslm_grads* vin,
@@ -746,6 +748,11 @@ static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gs
   int st = bind_all(view, gi, geom, binning, N, image, scratch, scratch_bytes, &b);
   if (st) return st;
   if (!vin || !y || !pixel_weight) { set_error("matvec: NULL argument"); return GSLM_ERR_INVALID; }
+  // GSLM_MV_LEAN: opts is the base of a gslm_matvec_opts_lean; <v, y> may stay as the gather's partials (dot_defer)
+  const gslm_cg_lean* lean = (opts && (opts->flags & GSLM_MV_LEAN))
+                                 ? &reinterpret_cast<const gslm_matvec_opts_lean*>(opts)->lean : nullptr;
+  if (lean && na < 0) { set_error("matvec: GSLM_MV_LEAN is an option of gslm_matvec_view_active"); return GSLM_ERR_INVALID; }
+  const bool dot_defer = lean && lean->dot_defer;
   const int32_t stages = (opts && opts->stages) ? opts->stages : GSLM_STAGE_ALL;
   const double* damp7 = opts ? opts->damp7 : nullptr;
   double* dot_out = opts ? opts->dot_vy : nullptr;
@@ -762,7 +769,11 @@ static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gs
       return GSLM_ERR_INVALID;
     }
   }
-  if (dot_out && (!opts->dot_scratch || opts->dot_scratch_bytes < gslm_dot_scratch_bytes(rows))) {
+  if (dot_defer && (!opts || dot_out)) {
+    set_error("matvec_view_active (GSLM_MV_LEAN): dot_defer leaves <v, y> as partials in dot_scratch (dot_vy must be NULL)");
+    return GSLM_ERR_INVALID;
+  }
+  if ((dot_out || dot_defer) && (!opts->dot_scratch || opts->dot_scratch_bytes < gslm_dot_scratch_bytes(rows))) {
     set_error("matvec: dot scratch too small");
     return GSLM_ERR_CAPACITY;
   }
@@ -794,6 +805,25 @@ static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gs
       return GSLM_ERR_INVALID;
     }
     if ((st = build_xpby(opts, vin, proj ? 3 : 3 * (b.g.M - 1), mask_xyz != 0, &xp))) return st;
+    if (lean && lean->beta_partials) {
+      if (lean->beta_np < 0 || lean->beta_partials == opts->dot_scratch) {
+        set_error("matvec_view_active (GSLM_MV_LEAN): beta's partials need a count and a buffer other than dot_scratch");
+        return GSLM_ERR_INVALID;
+      }
+      xp.num_part = (const double*)lean->beta_partials;
+      xp.num_np = lean->beta_np;
+      xp.num_store = lean->beta_store;
+    }
+  } else if (lean && lean->beta_partials) {
+    set_error("matvec_view_active (GSLM_MV_LEAN): beta's partials without the fused direction update (xpby_s)");
+    return GSLM_ERR_INVALID;
+  }
+  // the list-order parameter block (gslm_active_params): the ACTIVE kernels read row j of it, not row ids[j] of g
+  GaussK gp = b.g;
+  const uint32_t* clamp_list = nullptr;
+  if (lean && lean->params) {
+    if (!active) { set_error("matvec_view_active (GSLM_MV_LEAN): a parameter block belongs to an active list"); return GSLM_ERR_INVALID; }
+    clamp_list = active_params_bind(lean->params, na, &gp);
   }
   if (opts && opts->trec_in) {
     if (stages & GSLM_STAGE_TANGENT) {
@@ -808,8 +838,8 @@ static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gs
     return GSLM_ERR_INVALID;
   }
   if ((stages & GSLM_STAGE_TANGENT) &&
-      (st = launch_tangent_pre(b.v, b.g, t, nullptr, b.gb, b.sb, fused_xpby ? &xp : nullptr, s, mask_xyz != 0, ids,
-                               na)))
+      (st = launch_tangent_pre(b.v, gp, t, nullptr, b.gb, b.sb, fused_xpby ? &xp : nullptr, s, mask_xyz != 0, ids,
+                               na, clamp_list)))
     return st;
   float* jv_out = opts ? opts->jv_out : nullptr;
   if (jv_out) {
@@ -842,9 +872,10 @@ static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gs
     return launch_rowsum_screen(b.g, b.gb, b.sb, opts->screen_out, s);
   }
   if (!(stages & GSLM_STAGE_GATHER)) return GSLM_OK;
-  double* part = dot_out ? (double*)opts->dot_scratch : nullptr;
-  if ((st = launch_gather_lm(b.v, b.g, b.gb, b.sb, make_gradk(y), make_gradk(vin), damp7,
-                             (stages & GSLM_STAGE_OVERWRITE) != 0, mask_xyz != 0, part, s, proj, ids, na, hrow)))
+  double* part = (dot_out || dot_defer) ? (double*)opts->dot_scratch : nullptr;
+  if ((st = launch_gather_lm(b.v, gp, b.gb, b.sb, make_gradk(y), make_gradk(vin), damp7,
+                             (stages & GSLM_STAGE_OVERWRITE) != 0, mask_xyz != 0, part, s, proj, ids, na, hrow,
+                             clamp_list)))
     return st;
   if (dot_out) return gslm_dot_finalize(part, (int32_t)((rows + 255) / 256), dot_out, stream);
   return GSLM_OK;
@@ -866,6 +897,76 @@ int gslm_matvec_view_active(const gslm_view* view, const gslm_gaussians* gi, con
   if (n_active < 0) { set_error("matvec_view_active: negative n_active"); return GSLM_ERR_INVALID; }
   return matvec_view(view, gi, vin, pixel_weight, mask_xyz, geom, binning, N, image, scratch, scratch_bytes, y, opts,
                      active_ids, n_active, active_rows, stream);
+}
+
+// The list-order parameter block: [xyz 3 | raw scale 3 | raw rotation 4 | raw opacity 1] floats and the clamp
+// word, each an array over the na listed Gaussians -- everything chain_jvp / chain_vjp load per Gaussian on the LM
+// rows (xyz frozen: the primal SH coefficients are not read).
+static size_t active_params_layout(int64_t na, void* base, float** xyz, float** sc, float** rot, float** op,
+                                   uint32_t** cw) {
+  Carver c{(char*)base};
+  const int64_t n = na > 0 ? na : 1;
+  float* a = c.take<float>(3 * n);
+  float* b = c.take<float>(3 * n);
+  float* r = c.take<float>(4 * n);
+  float* o = c.take<float>(n);
+  uint32_t* w = c.take<uint32_t>(n);
+  if (xyz) { *xyz = a; *sc = b; *rot = r; *op = o; *cw = w; }
+  return c.off;
+}
+
+static const uint32_t* active_params_bind(const void* block, int64_t na, GaussK* g) {
+  float *xyz, *sc, *rot, *op;
+  uint32_t* cw;
+  active_params_layout(na, const_cast<void*>(block), &xyz, &sc, &rot, &op, &cw);
+  g->means3D = xyz;
+  g->scales = sc;
+  g->rot = rot;
+  g->opac = op;
+  return cw;
+}
+
+size_t gslm_active_params_bytes(int64_t n_active) {
+  return active_params_layout(n_active, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
+}
+
+int gslm_active_params(const gslm_gaussians* gi, const void* geom, int64_t P, const int32_t* active_ids,
+                       int64_t n_active, void* block, size_t block_bytes, int32_t* pos_dev, void* stream) {
+  if (!gi || !geom || P < 0 || n_active < 0 || n_active > P || !block || !pos_dev || (n_active > 0 && !active_ids)) {
+    set_error("active_params: NULL argument or 0 <= n_active <= P violated");
+    return GSLM_ERR_INVALID;
+  }
+  if (block_bytes < gslm_active_params_bytes(n_active)) {
+    set_error("active_params: block smaller than gslm_active_params_bytes(n_active)");
+    return GSLM_ERR_CAPACITY;
+  }
+  if (gi->P != P || !gi->raw || gi->cov3D_precomp || gi->colors_precomp ||
+      (P > 0 && (!gi->means3D || !gi->scales || !gi->rotations || !gi->opacities))) {
+    set_error("active_params: the raw GaussianModel leaves of the P Gaussians the list was built for");
+    return GSLM_ERR_INVALID;
+  }
+  GeomBufs gb;
+  geom_layout(P, const_cast<void*>(geom), &gb);
+  float *xyz, *sc, *rot, *op;
+  uint32_t* cw;
+  active_params_layout(n_active, block, &xyz, &sc, &rot, &op, &cw);
+  return launch_active_params(gi->means3D, gi->scales, gi->rotations, gi->opacities, gb.clampw, active_ids, n_active,
+                              P, xyz, sc, rot, op, cw, pos_dev, (hipStream_t)stream);
+}
+
+int gslm_cg_start_active(const float* g_full, const int32_t* active_ids, int64_t n_active, int64_t P,
+                         const int32_t* widths, int32_t ngroups, int64_t tail_n, int64_t lo, float* s, float* p,
+                         float* q, float* x, void* partials, void* stream) {
+  return launch_cg_start_active(g_full, active_ids, n_active, P, widths, ngroups, tail_n, lo, s, p, q, x,
+                                (double*)partials, (hipStream_t)stream);
+}
+
+int gslm_cg_end_active(const float* x, const float* p, const double* num_dev, const double* den_dev, int64_t lo,
+                       const int32_t* pos_dev, int64_t n_active, int64_t P, const int32_t* widths, int32_t ngroups,
+                       int64_t tail_n, float* out_full, const void* fin_partials, int32_t fin_np, double* fin_dev,
+                       void* stream) {
+  return launch_cg_end_active(x, p, num_dev, den_dev, lo, pos_dev, n_active, P, widths, ngroups, tail_n, out_full,
+                              (const double*)fin_partials, fin_np, fin_dev, (hipStream_t)stream);
 }
 
 // the active list's workspace: the flags / their scan [P], the scan's block sums, its total

@@ -16,9 +16,6 @@ struct Groups {
   int n;
 };
 
-constexpr int DOT_THREADS = 256;
-constexpr int DOT_BLOCKS = 1024;
-
 __device__ __forceinline__ double group_w(const Groups& g, int64_t i) {
   double w = 1.0;
   if (g.n > 0) {
@@ -28,18 +25,6 @@ __device__ __forceinline__ double group_w(const Groups& g, int64_t i) {
       if (k < g.n && i >= g.bound[k] && i < g.bound[k + 1]) w = g.damp[k];
   }
   return w;
-}
-
-__device__ __forceinline__ double block_sum_d(double x, double* s) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
-  if (lane == 0) s[w] = x;
-  __syncthreads();
-  double t = 0.0;
-  if (tid == 0)
-    for (int k = 0; k < DOT_THREADS / 64; ++k) t += s[k];
-  return t;
 }
 
 __global__ __launch_bounds__(DOT_THREADS) void k_dot_partial(const float* __restrict__ a, const float* __restrict__ b,
@@ -107,16 +92,23 @@ __global__ __launch_bounds__(256) void k_xpby_dev(int64_t n, const float* __rest
 // passes over x.
 // ctl (or NULL): the device CG control block of k_cg_monitor -- a stopped solve, or delta < 1e-20 (the
 // reference's early termination, conjugate_gradient.py:88-91, before x moves), leaves x and s untouched.
-template <bool MONITOR>
+// PARTS (gslm_cg_update_lean): delta arrives as the gather's block partials (dels; load_scalar) instead of the
+// finished scalar at del, and block 0 stores it to its slot; gamma (gams) is the finished scalar or, after a start,
+// partials too.  part must not be a buffer those partials are in.
+template <bool MONITOR, bool PARTS = false>
 __global__ __launch_bounds__(DOT_THREADS) void k_cg_update(int64_t n, const double* __restrict__ gam,
                                                            const double* __restrict__ del,
                                                            const float* __restrict__ p, const float* __restrict__ q,
                                                            float* __restrict__ x, float* __restrict__ s,
                                                            const float* __restrict__ g, double* __restrict__ part,
-                                                           const double* __restrict__ ctl) {
-  __shared__ double sm[DOT_THREADS / 64];
+                                                           const double* __restrict__ ctl, ScalarK gams,
+                                                           ScalarK dels) {
+  __shared__ double sm[DOT_THREADS / 64 + 1];
   if (ctl && (ctl[0] != 0.0 || *del < 1e-20 || !isfinite(*del))) return;  // a NaN delta: x kept (stop 4 below)
-  const float a = (float)((*gam) / (*del));
+  const double gv = PARTS ? load_scalar(gams, sm) : *gam;
+  const double dv = PARTS ? load_scalar(dels, sm) : *del;
+  if (PARTS) __syncthreads();  // sm is reused by the sums below
+  const float a = (float)(gv / dv);
   double acc = 0.0, axg = 0.0, axs = 0.0;
   const int64_t n4 = n / 4;
   const int64_t stride = (int64_t)gridDim.x * DOT_THREADS;
@@ -265,8 +257,29 @@ int gslm_cg_update(int64_t n, const double* gam_dev, const double* del_dev, cons
   }
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_cg_update<false>, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, st, n, gam_dev, del_dev, p, q, x, s,
-                     nullptr, (double*)scratch, (const double*)nullptr);
+                     nullptr, (double*)scratch, (const double*)nullptr, ScalarK{}, ScalarK{});
   hipLaunchKernelGGL(k_dot_final, dim3(1), dim3(DOT_THREADS), 0, st, (const double*)scratch, DOT_BLOCKS, gam_new_dev);
+  GSLM_LAUNCH_CHECK();
+  return GSLM_OK;
+}
+
+int gslm_cg_update_lean(int64_t n, double* gam_dev, const void* gam_partials, int32_t gam_np,
+                        const void* del_partials, int32_t del_np, double* del_dev, const float* p, const float* q,
+                        float* s, void* partials_out, void* stream) {
+  if (!gam_dev || gam_np < 0 || !del_partials || del_np < 0 || !partials_out || partials_out == del_partials ||
+      partials_out == gam_partials) {
+    set_error("gslm_cg_update_lean: NULL scalar / partials, or the new partials in a buffer of the old ones");
+    return GSLM_ERR_INVALID;
+  }
+  if ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(s)) & 15) {
+    set_error("gslm_cg_update_lean: vectors must be 16-byte aligned");
+    return GSLM_ERR_INVALID;
+  }
+  const ScalarK gams{gam_dev, (const double*)gam_partials, gam_np, gam_dev};
+  const ScalarK dels{nullptr, (const double*)del_partials, del_np, del_dev};
+  hipLaunchKernelGGL((k_cg_update<false, true>), dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, (hipStream_t)stream, n,
+                     (const double*)gam_dev, (const double*)nullptr, p, q, (float*)nullptr, s, (const float*)nullptr,
+                     (double*)partials_out, (const double*)nullptr, gams, dels);
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
 }
@@ -286,7 +299,7 @@ int gslm_cg_update_monitor(int64_t n, const double* gam_dev, const double* del_d
   hipStream_t st = (hipStream_t)stream;
   const double* part = (const double*)scratch;
   hipLaunchKernelGGL(k_cg_update<true>, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, st, n, gam_dev, del_dev, p, q, x, s, g,
-                     (double*)scratch, cg_ctl);
+                     (double*)scratch, cg_ctl, ScalarK{}, ScalarK{});
   hipLaunchKernelGGL(k_dot_final3, dim3(3), dim3(DOT_THREADS), 0, st, part, DOT_BLOCKS, gam_new_dev, xg_dev, xs_dev);
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;

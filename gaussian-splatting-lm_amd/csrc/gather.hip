@@ -126,7 +126,8 @@ __global__ __launch_bounds__(256, PROJ ? 5 : 1) void k_gather_lm(ViewK v, GaussK
                                                     const uint32_t* __restrict__ hscan,
                                                     const float4* __restrict__ rows, FlatK o,
                                                     const int32_t* __restrict__ ids, int64_t na,
-                                                    const uint32_t* __restrict__ hrow) {
+                                                    const uint32_t* __restrict__ hrow,
+                                                    const uint32_t* __restrict__ clamp_list) {
   o.rest_proj = PROJ ? 1 : 0;  // the launcher picked the variant from it
   if (cg_stopped(v)) return;
   extern __shared__ __attribute__((aligned(16))) float s_rest[];  // row chunks, then the factored SH stage
@@ -154,7 +155,9 @@ __global__ __launch_bounds__(256, PROJ ? 5 : 1) void k_gather_lm(ViewK v, GaussK
     block_sum_rows<ROWF4>(rows, R0, R1, h0, h1 - h0, reinterpret_cast<float4*>(s_rest), G2);
   }
   ChainOut co;
-  if (valid) chain_vjp<true>(v, g, i, n != 0, n ? clampw[i] : 0u, G2, WANT_MEANS, co);
+  // clamp_list (gslm_active_params): g's parameter arrays and the clamp words are the list's own, row j
+  const bool listed = ACTIVE && clamp_list != nullptr;
+  if (valid) chain_vjp<true>(v, g, listed ? j : i, n != 0, n ? (listed ? clamp_list[j] : clampw[i]) : 0u, G2, WANT_MEANS, co);
   if (ACTIVE) g.P = na;  // the epilogue writes rows j < na of y (it reads P and M of g only)
   lm_epilogue<WANT_MEANS, true>((v.D + 1) * (v.D + 1), g, co, o, s_rest, s_dot);
 }
@@ -248,7 +251,8 @@ int launch_preprocess_bwd(const ViewK& v, const GaussK& g, const GeomBufs& gb, c
 
 int launch_gather_lm(const ViewK& v, const GaussK& g, const GeomBufs& gb, const ScratchBufs& sb, const GradK& y,
                      const GradK& vin, const double* damp7, bool overwrite, bool mask_xyz, double* dot_part,
-                     hipStream_t s, bool rest_proj, const int32_t* ids, int64_t na, const uint32_t* hrow) {
+                     hipStream_t s, bool rest_proj, const int32_t* ids, int64_t na, const uint32_t* hrow,
+                     const uint32_t* clamp_list) {
   const bool active = na >= 0;
   const int64_t nrows = active ? na : g.P;
   if (nrows == 0) return GSLM_OK;
@@ -265,22 +269,22 @@ int launch_gather_lm(const ViewK& v, const GaussK& g, const GeomBufs& gb, const 
   const size_t lds = (rest_lds > chunk_lds ? rest_lds : chunk_lds) + 16;
   if (active && o.rest_proj)
     hipLaunchKernelGGL((k_gather_lm<false, 2, true, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles,
-                       gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow);
+                       gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow, clamp_list);
   else if (active)
     hipLaunchKernelGGL((k_gather_lm<false, 2, false, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles,
-                       gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow);
+                       gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow, clamp_list);
   else if (mask_xyz && o.rest_proj)
     hipLaunchKernelGGL((k_gather_lm<false, 2, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr);
+                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr);
   else if (mask_xyz)
     hipLaunchKernelGGL((k_gather_lm<false, 2, false>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr);
+                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr);
   else if (o.rest_proj)
     hipLaunchKernelGGL((k_gather_lm<true, 3, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr);
+                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr);
   else
     hipLaunchKernelGGL((k_gather_lm<true, 3, false>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr);
+                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr);
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
 }
@@ -335,6 +339,214 @@ int launch_active_pack(bool to_active, const float* src, float* dst, const int32
   const unsigned nb = (unsigned)((total + 255) / 256);
   if (to_active) hipLaunchKernelGGL(k_active_pack<true>, dim3(nb), dim3(256), 0, s, k, ids, na, src, dst);
   else hipLaunchKernelGGL(k_active_pack<false>, dim3(nb), dim3(256), 0, s, k, ids, na, src, dst);
+  GSLM_LAUNCH_CHECK();
+  return GSLM_OK;
+}
+
+// ---- the list-order parameter block (gslm_active_params) ----
+__global__ __launch_bounds__(256) void k_active_params(const float* __restrict__ means3D, const float* __restrict__ scales,
+                                                        const float* __restrict__ rot, const float* __restrict__ opac,
+                                                        const uint32_t* __restrict__ clampw,
+                                                        const int32_t* __restrict__ ids, int64_t na,
+                                                        float* __restrict__ xyz_l, float* __restrict__ scales_l,
+                                                        float* __restrict__ rot_l, float* __restrict__ opac_l,
+                                                        uint32_t* __restrict__ clamp_l, int32_t* __restrict__ pos) {
+  const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= na) return;
+  const int64_t i = ids[j];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    xyz_l[3 * j + k] = means3D[3 * i + k];
+    scales_l[3 * j + k] = scales[3 * i + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 4; ++k) rot_l[4 * j + k] = rot[4 * i + k];
+  opac_l[j] = opac[i];
+  clamp_l[j] = clampw[i];
+  pos[i] = (int32_t)j;
+}
+
+int launch_active_params(const float* means3D, const float* scales, const float* rot, const float* opac,
+                         const uint32_t* clampw, const int32_t* ids, int64_t na, int64_t P, float* xyz_l,
+                         float* scales_l, float* rot_l, float* opac_l, uint32_t* clamp_l, int32_t* pos, hipStream_t s) {
+  if (P > 0) GSLM_HIP_CHECK(hipMemsetAsync(pos, 0xFF, (size_t)P * sizeof(int32_t), s));  // -1: not listed
+  if (na == 0) return GSLM_OK;
+  hipLaunchKernelGGL(k_active_params, dim3((unsigned)((na + 255) / 256)), dim3(256), 0, s, means3D, scales, rot, opac,
+                     clampw, ids, na, xyz_l, scales_l, rot_l, opac_l, clamp_l, pos);
+  GSLM_LAUNCH_CHECK();
+  return GSLM_OK;
+}
+
+// ---- the lean CG loop's first and last launch (gslm_cg_start_active / gslm_cg_end_active) ----
+static int make_packk(const char* who, const int32_t* widths, int ngroups, int64_t na, int64_t P, PackK* k, int64_t* po,
+                      int64_t* ao) {
+  if (ngroups < 1 || ngroups > 8 || !widths || na < 0 || na > P) {
+    set_error(std::string(who) + ": 1..8 groups, 0 <= n_active <= P");
+    return GSLM_ERR_INVALID;
+  }
+  *k = PackK{};
+  *po = *ao = 0;
+  for (int q = 0; q < ngroups; ++q) {
+    if (widths[q] < 0) { set_error(std::string(who) + ": negative group width"); return GSLM_ERR_INVALID; }
+    k->w[q] = widths[q];
+    k->poff[q] = *po;
+    k->aoff[q] = *ao;
+    *po += P * widths[q];
+    *ao += na * widths[q];
+    k->wsum += widths[q];
+  }
+  k->n = ngroups;
+  return GSLM_OK;
+}
+
+// r / w and r % w of a non-negative r: 32-bit when r fits (every layout the solver meets), 64-bit otherwise
+__device__ __forceinline__ void divmod_w(int64_t r, int w, int64_t& d, int& c) {
+  if (r < ((int64_t)1 << 32)) {
+    // (the solver's widths as constants: a multiply or a shift instead of the division loop)
+    const uint32_t d32 = w == 3 ? (uint32_t)r / 3u : w == 4 ? (uint32_t)r / 4u : w == 1 ? (uint32_t)r
+                                                                                         : (uint32_t)r / (uint32_t)w;
+    d = d32;
+    c = (int)((uint32_t)r - d32 * (uint32_t)w);
+  } else {
+    d = r / w;
+    c = (int)(r - d * w);
+  }
+}
+
+// The solve's start in one pass over the list layout: s = p = (the listed rows of the full-layout g), q = x = 0 on
+// [lo, n), and the partials of gamma_0 = <s, s> over [lo, n) with k_dot_partial's element-to-thread mapping
+// (DOT_BLOCKS blocks of DOT_THREADS, element lo + b DOT_THREADS + t + m stride in order of m), so the finished sum
+// is bitwise gslm_dot's.  The head [0, lo) (the masked xyz group) is zeroed in all four.
+__global__ __launch_bounds__(DOT_THREADS) void k_cg_start_active(PackK k, const int32_t* __restrict__ ids, int64_t lo,
+                                                                  int64_t ao, int64_t po, int64_t tail_n,
+                                                                  const float* __restrict__ gf, float* __restrict__ s,
+                                                                  float* __restrict__ p, float* __restrict__ q,
+                                                                  float* __restrict__ x, double* __restrict__ part) {
+  __shared__ double sm[DOT_THREADS / 64];
+  const int64_t n = ao + tail_n;
+  const int64_t stride = (int64_t)gridDim.x * DOT_THREADS;
+  const int64_t t0 = (int64_t)blockIdx.x * DOT_THREADS + threadIdx.x;
+  for (int64_t m = t0; m < lo; m += stride) s[m] = p[m] = q[m] = x[m] = 0.f;
+  double acc = 0.0;
+  constexpr int U = 4;  // elements of a thread in flight (two dependent loads each); summed in their order
+  for (int64_t m0 = lo + t0; m0 < n; m0 += U * stride) {
+    float v[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t m = m0 + u * stride;
+      v[u] = 0.f;
+      if (m >= n) continue;
+      if (m >= ao) {
+        v[u] = gf[po + (m - ao)];
+      } else {
+        int grp = 0;
+        while (grp < k.n - 1 && m >= k.aoff[grp + 1]) ++grp;
+        int64_t j;
+        int c;
+        divmod_w(m - k.aoff[grp], k.w[grp], j, c);
+        v[u] = gf[k.poff[grp] + (int64_t)ids[j] * k.w[grp] + c];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int64_t m = m0 + u * stride;
+      if (m >= n) continue;
+      s[m] = v[u];
+      p[m] = v[u];
+      q[m] = 0.f;
+      x[m] = 0.f;
+      acc += (double)v[u] * (double)v[u];
+    }
+  }
+  const double t = block_sum_d(acc, sm);
+  if (threadIdx.x == 0) part[blockIdx.x] = t;
+}
+
+int launch_cg_start_active(const float* g_full, const int32_t* ids, int64_t na, int64_t P, const int32_t* widths,
+                           int ngroups, int64_t tail_n, int64_t lo, float* s_, float* p, float* q, float* x,
+                           double* part, hipStream_t s) {
+  PackK k;
+  int64_t po, ao;
+  int st = make_packk("cg_start_active", widths, ngroups, na, P, &k, &po, &ao);
+  if (st) return st;
+  if (!g_full || !s_ || !p || !q || !x || !part || (na > 0 && !ids) || tail_n < 0 || lo < 0 || lo > ao + tail_n) {
+    set_error("cg_start_active: NULL buffer, negative tail or lo outside [0, n]");
+    return GSLM_ERR_INVALID;
+  }
+  hipLaunchKernelGGL(k_cg_start_active, dim3(DOT_BLOCKS), dim3(DOT_THREADS), 0, s, k, ids, lo, ao, po, tail_n, g_full, s_,
+                     p, q, x, part);
+  GSLM_LAUNCH_CHECK();
+  return GSLM_OK;
+}
+
+// The solve's end in one pass over the full-layout output: thread (group blockIdx.y, Gaussian i) writes the row's
+// floats -- x + a p of list row pos[i] (a = num / den, k_axpy_dev's arithmetic, applied on [lo, n) as the solve's
+// last deferred update is), or +0.0f when i is not listed; the blocks of the row past the groups copy the tail.
+// Block (0, 0) also finishes the last gamma' into its slot (nobody else will read those partials).
+__global__ __launch_bounds__(DOT_THREADS) void k_cg_end_active(PackK k, const int32_t* __restrict__ pos, int64_t P,
+                                                                int64_t lo, int64_t ao, int64_t po, int64_t tail_n,
+                                                                const float* __restrict__ x, const float* __restrict__ p,
+                                                                const double* __restrict__ num,
+                                                                const double* __restrict__ den, float* __restrict__ out,
+                                                                ScalarK fin) {
+  __shared__ double sm[DOT_THREADS / 64 + 1];
+  if (blockIdx.x == 0 && blockIdx.y == 0 && fin.part) load_scalar(fin, sm);  // (block-uniform)
+  float af = 0.f;
+  if (num) {
+    const double a = den ? (*num) / (*den) : (*num);
+    af = (float)(a * (double)1.0f);
+  }
+  const int grp = blockIdx.y;
+  if (grp == k.n) {
+    const int64_t stride = (int64_t)gridDim.x * DOT_THREADS;
+    for (int64_t e = (int64_t)blockIdx.x * DOT_THREADS + threadIdx.x; e < tail_n; e += stride) {
+      const int64_t m = ao + e;
+      float v = x[m];
+      if (num && m >= lo) v = v + af * p[m];
+      out[po + e] = v;
+    }
+    return;
+  }
+  const int64_t i = (int64_t)blockIdx.x * DOT_THREADS + threadIdx.x;
+  if (i >= P) return;
+  const int w = k.w[grp];
+  const int32_t j = pos[i];
+  float* o = out + k.poff[grp] + i * w;
+  if (j < 0) {
+    for (int c = 0; c < w; ++c) o[c] = 0.f;
+    return;
+  }
+  const int64_t m0 = k.aoff[grp] + (int64_t)j * w;
+  for (int c0 = 0; c0 < w; c0 += 4) {
+    float xv[4], pv[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const bool on = c0 + c < w;
+      xv[c] = on ? x[m0 + c0 + c] : 0.f;
+      pv[c] = (on && num && m0 + c0 + c >= lo) ? p[m0 + c0 + c] : 0.f;
+    }
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      if (c0 + c < w) o[c0 + c] = (num && m0 + c0 + c >= lo) ? xv[c] + af * pv[c] : xv[c];
+  }
+}
+
+int launch_cg_end_active(const float* x, const float* p, const double* num, const double* den, int64_t lo,
+                         const int32_t* pos, int64_t na, int64_t P, const int32_t* widths, int ngroups,
+                         int64_t tail_n, float* out, const double* fin_part, int fin_np, double* fin_dev,
+                         hipStream_t s) {
+  PackK k;
+  int64_t po, ao;
+  int st = make_packk("cg_end_active", widths, ngroups, na, P, &k, &po, &ao);
+  if (st) return st;
+  if (!x || !out || (num && !p) || (P > 0 && !pos) || tail_n < 0 || lo < 0 || (fin_part && (fin_np < 0 || !fin_dev))) {
+    set_error("cg_end_active: NULL buffer, negative tail or lo, or partials without a slot for their sum");
+    return GSLM_ERR_INVALID;
+  }
+  int64_t nb = (P + DOT_THREADS - 1) / DOT_THREADS;
+  nb = nb < 1 ? 1 : nb;
+  hipLaunchKernelGGL(k_cg_end_active, dim3((unsigned)nb, (unsigned)(k.n + 1)), dim3(DOT_THREADS), 0, s, k, pos, P, lo, ao,
+                     po, tail_n, x, p, num, den, out, ScalarK{nullptr, fin_part, fin_np, fin_dev});
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
 }

@@ -58,10 +58,10 @@ struct ViewK {
 // time: one memory latency per 8 partials, where the one-at-a-time loop waited on every load.  The additions keep
 // that loop's order (a skipped slot adds nothing), so the sum is bitwise the same -- the deterministic reductions'
 // contract.
+// T: the number of threads that share the sum (threads 0 .. T - 1 of the block call it)
 template <typename F>
-__device__ __forceinline__ F strided_sum_in_order(const F* __restrict__ x, int64_t n) {
+__device__ __forceinline__ F strided_sum_in_order(const F* __restrict__ x, int64_t n, int64_t T) {
   F acc = F(0);
-  const int64_t T = blockDim.x;
   for (int64_t i = threadIdx.x; i < n; i += 8 * T) {
     F v[8];
 #pragma unroll
@@ -71,6 +71,10 @@ __device__ __forceinline__ F strided_sum_in_order(const F* __restrict__ x, int64
       if (i + k * T < n) acc += v[k];
   }
   return acc;
+}
+template <typename F>
+__device__ __forceinline__ F strided_sum_in_order(const F* __restrict__ x, int64_t n) {
+  return strided_sum_in_order(x, n, (int64_t)blockDim.x);
 }
 
 __device__ __forceinline__ float clamp01(float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); }

@@ -47,6 +47,57 @@ int launch_failed(hipError_t e, const char* file, int line);  // sets the error 
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
 
+// ---------------- the CG drivers' two-pass dots (cg.hip) ----------------
+constexpr int DOT_THREADS = 256;
+constexpr int DOT_BLOCKS = 1024;
+
+// Sum over a block of DOT_THREADS threads, valid in thread 0: wave shuffles, then the wave sums in order.
+__device__ __forceinline__ double block_sum_d(double x, double* s) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o, 64);
+  if (lane == 0) s[w] = x;
+  __syncthreads();
+  double t = 0.0;
+  if (tid == 0)
+    for (int k = 0; k < DOT_THREADS / 64; ++k) t += s[k];
+  return t;
+}
+
+// A device scalar that a consumer kernel may be handed before it is finished: either the finished double (v), or
+// the np block partials it is the sum of (part).  Every block of the consumer sums the partials itself -- the
+// additions of k_dot_final in k_dot_final's order, so the value is bitwise the one that launch would have stored --
+// and block 0 stores it to `store` (or NULL) for whoever reads the slot after this kernel.  The kernel boundary
+// behind the producer of the partials is the only synchronisation.
+struct ScalarK {
+  const double* v;
+  const double* part;
+  int np;
+  double* store;
+};
+inline ScalarK scalar_of(const double* v) { return ScalarK{v, nullptr, 0, nullptr}; }
+
+// Called by every thread of a block of at least DOT_THREADS threads (whole waves); sm: DOT_THREADS / 64 + 1 doubles.
+// The first DOT_THREADS threads do k_dot_final's sum; every thread returns it.
+__device__ __forceinline__ double load_scalar(const ScalarK& k, double* sm) {
+  if (!k.part) return *k.v;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  double acc = 0.0;
+  if (tid < DOT_THREADS) acc = strided_sum_in_order(k.part, k.np, DOT_THREADS);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if (lane == 0 && w < DOT_THREADS / 64) sm[w] = acc;
+  __syncthreads();
+  if (tid == 0) {
+    double t = 0.0;
+    for (int q = 0; q < DOT_THREADS / 64; ++q) t += sm[q];
+    sm[DOT_THREADS / 64] = t;
+    if (k.store && blockIdx.x == 0) *k.store = t;
+  }
+  __syncthreads();
+  return sm[DOT_THREADS / 64];
+}
+
 // ---------------- radix sort (LSD, 8-bit digits, stable) ----------------
 constexpr int SORT_THREADS = 256;
 constexpr int SORT_ITEMS = 16;                       // items per thread per block (large sorts)

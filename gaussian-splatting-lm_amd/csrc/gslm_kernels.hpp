@@ -581,12 +581,17 @@ struct XpbyK {
   const double* anum;
   const double* aden;
   int64_t xoff;
+  // num not yet finished (gslm_cg_lean): its num_np block partials, summed by every block (load_scalar), and the
+  // slot block 0 stores the sum to (num_part == NULL: num is the finished scalar)
+  const double* num_part;
+  int num_np;
+  double* num_store;
 };
 // compact: the LM rows' 8-float tangent records (store_trec, tangent.hip) instead of 12 floats
 // na >= 0 (gslm_matvec_view_active): one thread per listed Gaussian; t's and xp's groups hold the na listed rows
 int launch_tangent_pre(const ViewK& v, const GaussK& g, const GaussK& t, const float* m2t, const GeomBufs& gb,
                        const ScratchBufs& sb, const XpbyK* xp, hipStream_t s, bool compact,
-                       const int32_t* ids = nullptr, int64_t na = -1);
+                       const int32_t* ids = nullptr, int64_t na = -1, const uint32_t* clamp_list = nullptr);
 int launch_rowsum_screen(const GaussK& g, const GeomBufs& gb, const ScratchBufs& sb, float* out, hipStream_t s);
 constexpr int MAX_SCREEN_VIEWS = 16;
 constexpr int MAX_REST_VIEWS = GSLM_MAX_REST_VIEWS;
@@ -629,7 +634,20 @@ int launch_matvec_render(const ViewK& v, const GaussK& t, const GeomBufs& gb, co
 int launch_gather_lm(const ViewK& v, const GaussK& g, const GeomBufs& gb, const ScratchBufs& sb, const GradK& y,
                      const GradK& vin, const double* damp7, bool overwrite, bool mask_xyz, double* dot_part,
                      hipStream_t s, bool rest_proj = false, const int32_t* ids = nullptr, int64_t na = -1,
-                     const uint32_t* hrow = nullptr);
+                     const uint32_t* hrow = nullptr, const uint32_t* clamp_list = nullptr);
+// the list-order copy of what the chains load per Gaussian (gslm_active_params) and the inverse map pos [P]
+// (pos[ids[j]] = j, -1 off the list)
+int launch_active_params(const float* means3D, const float* scales, const float* rot, const float* opac,
+                         const uint32_t* clampw, const int32_t* ids, int64_t na, int64_t P, float* xyz_l,
+                         float* scales_l, float* rot_l, float* opac_l, uint32_t* clamp_l, int32_t* pos, hipStream_t s);
+// the lean CG loop's first and last launch (gslm_cg_start_active / gslm_cg_end_active)
+int launch_cg_start_active(const float* g_full, const int32_t* ids, int64_t na, int64_t P, const int32_t* widths,
+                           int ngroups, int64_t tail_n, int64_t lo, float* s_, float* p, float* q, float* x,
+                           double* part, hipStream_t s);
+int launch_cg_end_active(const float* x, const float* p, const double* num, const double* den, int64_t lo,
+                         const int32_t* pos, int64_t na, int64_t P, const int32_t* widths, int ngroups,
+                         int64_t tail_n, float* out, const double* fin_part, int fin_np, double* fin_dev,
+                         hipStream_t s);
 // a flat vector's groups ([rows x widths[k]], then a copied tail) between the P layout and an active list's
 int launch_active_pack(bool to_active, const float* src, float* dst, const int32_t* ids, int64_t na, int64_t P,
                        const int32_t* widths, int ngroups, int64_t tail_n, hipStream_t s);

@@ -16,7 +16,9 @@ namespace gslm {
 // every s / p / x load of the block in flight before the first store -- instead of one latency per group; a
 // full-layout SH rest (3(M-1) floats per Gaussian) streams in its own loop.
 __device__ __forceinline__ void block_xpby(const XpbyK& xp, int64_t P, float* s_rest) {
-  const float b = (float)((*xp.num) / (*xp.den));
+  // beta's numerator may still be the update kernel's block partials (XpbyK::num_part; load_scalar)
+  __shared__ double s_fin[DOT_THREADS / 64 + 1];
+  const float b = (float)(load_scalar(ScalarK{xp.num, xp.num_part, xp.num_np, xp.num_store}, s_fin) / (*xp.den));
   const bool with_x = xp.anum != nullptr;
   const float a = with_x ? (float)((*xp.anum) / (*xp.aden)) : 0.f;  // gslm_cg_update's alpha, bitwise
   const int64_t i0 = (int64_t)blockIdx.x * blockDim.x;
@@ -103,13 +105,15 @@ __device__ __forceinline__ void store_trec(float4* __restrict__ out, int64_t i, 
 
 // ACTIVE (gslm_matvec_view_active): thread j handles Gaussian ids[j] of the scene (parameters, clamp word, tile
 // count, tangent record) and row j of the tangent's groups and of the fused direction update, which hold the na
-// listed Gaussians only.  Same arithmetic per Gaussian as the full-layout kernel.
+// listed Gaussians only.  Same arithmetic per Gaussian as the full-layout kernel.  With clamp_list the parameters
+// and the clamp word are read from row j of the list-order copy (gslm_active_params) instead of row ids[j].
 template <bool RAW, bool XPBY, bool ACTIVE = false>
 __global__ __launch_bounds__(256) void k_preprocess_jvp(ViewK v, GaussK g, GaussK t, const float* __restrict__ m2t,
                                                          const uint32_t* __restrict__ clampw,
                                                          const uint32_t* __restrict__ tiles,
                                                          float4* __restrict__ trec, XpbyK xp, int compact,
-                                                         int lead, const int32_t* __restrict__ ids, int64_t na) {
+                                                         int lead, const int32_t* __restrict__ ids, int64_t na,
+                                                         const uint32_t* __restrict__ clamp_list) {
   extern __shared__ __attribute__((aligned(16))) float s_rest[];  // XPBY: [256 * 3(M-1)]; lead >= 0: [256 * rest_stride]
   if (cg_stopped(v)) return;
   const int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -134,14 +138,16 @@ __global__ __launch_bounds__(256) void k_preprocess_jvp(ViewK v, GaussK g, Gauss
   const int64_t i = ACTIVE ? (int64_t)ids[j] : j;
   if (!ACTIVE && tiles[i] == 0) return;  // never gathered by the render passes (a listed Gaussian always is)
   float T2[10];
-  chain_jvp<RAW>(v, g, t, m2t, i, j, clampw[i], T2);
+  // clamp_list (gslm_active_params): g's parameter arrays and the clamp words are the list's own, row j
+  const bool listed = ACTIVE && clamp_list != nullptr;
+  chain_jvp<RAW>(v, g, t, m2t, listed ? j : i, j, listed ? clamp_list[j] : clampw[i], T2);
   store_trec(trec, i, T2, compact != 0);
 }
 
 // ------------------------------------------------------------------ launcher
 int launch_tangent_pre(const ViewK& v, const GaussK& g, const GaussK& t, const float* m2t, const GeomBufs& gb,
                        const ScratchBufs& sb, const XpbyK* xp, hipStream_t s, bool compact, const int32_t* ids,
-                       int64_t na) {
+                       int64_t na, const uint32_t* clamp_list) {
   const bool active = na >= 0;
   const int64_t n = active ? na : g.P;
   // no rows with a fused direction update: one block still applies the flat tail's update (block_xpby)
@@ -161,25 +167,25 @@ int launch_tangent_pre(const ViewK& v, const GaussK& g, const GaussK& t, const f
     const size_t lds = (size_t)256 * xp->w[2] * sizeof(float);
     if (active)
       hipLaunchKernelGGL((k_preprocess_jvp<true, true, true>), dim3(nb), dim3(256), lds, s, v, g, t, m2t, gb.clampw,
-                         gb.tiles, sb.trec, x, compact ? 1 : 0, -1, ids, na);
+                         gb.tiles, sb.trec, x, compact ? 1 : 0, -1, ids, na, clamp_list);
     else if (g.raw)
       hipLaunchKernelGGL((k_preprocess_jvp<true, true>), dim3(nb), dim3(256), lds, s, v, g, t, m2t, gb.clampw, gb.tiles,
-                         sb.trec, x, compact ? 1 : 0, -1, nullptr, -1);
+                         sb.trec, x, compact ? 1 : 0, -1, nullptr, -1, nullptr);
     else
       hipLaunchKernelGGL((k_preprocess_jvp<false, true>), dim3(nb), dim3(256), lds, s, v, g, t, m2t, gb.clampw, gb.tiles,
-                         sb.trec, x, compact ? 1 : 0, -1, nullptr, -1);
+                         sb.trec, x, compact ? 1 : 0, -1, nullptr, -1, nullptr);
   } else if (active) {
     hipLaunchKernelGGL((k_preprocess_jvp<true, false, true>), dim3(nb), dim3(256), 0, s, v, g, t, m2t, gb.clampw,
-                       gb.tiles, sb.trec, x, compact ? 1 : 0, -1, ids, na);
+                       gb.tiles, sb.trec, x, compact ? 1 : 0, -1, ids, na, clamp_list);
   } else {
     const int lead = g.P > 0 ? stage_lead(g) : -1;
     const size_t lds = lead >= 0 ? (size_t)256 * g.rest_stride * sizeof(float) : 0;
     if (g.raw)
       hipLaunchKernelGGL((k_preprocess_jvp<true, false>), dim3(nb), dim3(256), lds, s, v, g, t, m2t, gb.clampw, gb.tiles,
-                         sb.trec, x, compact ? 1 : 0, lead, nullptr, -1);
+                         sb.trec, x, compact ? 1 : 0, lead, nullptr, -1, nullptr);
     else
       hipLaunchKernelGGL((k_preprocess_jvp<false, false>), dim3(nb), dim3(256), lds, s, v, g, t, m2t, gb.clampw, gb.tiles,
-                         sb.trec, x, compact ? 1 : 0, lead, nullptr, -1);
+                         sb.trec, x, compact ? 1 : 0, lead, nullptr, -1, nullptr);
   }
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;

@@ -67,6 +67,19 @@ class GslmMatvecOpts(ctypes.Structure):
     ]
 
 
+class GslmCgLean(ctypes.Structure):
+    """gslm_cg_lean: the lean single-view CG loop's options for gslm_matvec_view_lean."""
+    _fields_ = [
+        ("beta_partials", ctypes.c_void_p), ("beta_np", ctypes.c_int32), ("dot_defer", ctypes.c_int32),
+        ("beta_store", ctypes.c_void_p), ("params", ctypes.c_void_p),
+    ]
+
+
+class GslmMatvecOptsLean(ctypes.Structure):
+    """gslm_matvec_opts_lean: gslm_matvec_view_active's options with GSLM_MV_LEAN set in base.flags."""
+    _fields_ = [("base", GslmMatvecOpts), ("lean", GslmCgLean)]
+
+
 class GslmViewWs(ctypes.Structure):
     """gslm_view_ws: one view's workspaces for gslm_gather_views."""
     _fields_ = [
@@ -183,6 +196,22 @@ EXPORTS = {
     "gslm_active_unpack": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                           ctypes.c_int64, ctypes.POINTER(ctypes.c_int32), ctypes.c_int32,
                                           ctypes.c_int64, ctypes.c_void_p]),
+    "gslm_active_params_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "gslm_active_params": (ctypes.c_int, [ctypes.POINTER(GslmGaussians), ctypes.c_void_p, ctypes.c_int64,
+                                          ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_size_t,
+                                          ctypes.c_void_p, ctypes.c_void_p]),
+    "gslm_cg_start_active": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                            ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int64,
+                                            ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gslm_cg_update_lean": (ctypes.c_int, [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32,
+                                           ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+    "gslm_cg_end_active": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                          ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64,
+                                          ctypes.POINTER(ctypes.c_int32), ctypes.c_int32, ctypes.c_int64,
+                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p,
+                                          ctypes.c_void_p]),
     "gslm_rest_basis": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int32, ctypes.POINTER(GslmGaussians),
                                        ctypes.c_void_p, ctypes.c_void_p]),
     "gslm_rest_coords": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int32, ctypes.POINTER(GslmGaussians),

@@ -31,6 +31,7 @@ STAGE_ALL = 7
 STAGE_OVERWRITE = 8
 MV_TAIL_CLEAN = 1  # gslm_matvec_opts.flags: GSLM_MV_TAIL_CLEAN
 MV_SH_REST_PROJECTED = 2  # GSLM_MV_SH_REST_PROJECTED
+MV_LEAN = 4  # GSLM_MV_LEAN
 
 DEFAULT_DAMP = {"xyz": 5e2, "features_dc": 5e-2, "features_rest": 5e-2, "scaling": 5e-2, "rotation": 5e-2,
                 "opacity": 5e-2, "exposure": 1e1}
@@ -48,6 +49,7 @@ class ViewRaster:
         # the scratch's gradient rows of never-blended entries hold the zeros of an earlier fused
         # product on the current geometry (GSLM_MV_TAIL_CLEAN): false after a forward or a backward
         self._active = None
+        self._params = None
         self.tail_clean = False
         self.epoch = 0  # forwards so far: a right-hand side belongs to the geometry of one of them
 
@@ -60,6 +62,7 @@ class ViewRaster:
         self._tail_clean = bool(value)
         if not value:
             self._active = None  # the active list is the row map's: it lives exactly as long
+            self._params = None  # ... and so does the list-order parameter block
 
     def active_list(self, P, stream):
         """(ids, Pa): the ascending int32 ids of the Gaussians that own a head row of this view's LM row map
@@ -81,6 +84,25 @@ class ViewRaster:
             self._active = (ids[:n], n)
             self.active_rows = rows[:n + 1]  # entry j's head rows: [rows[j], rows[j + 1])
         return self._active
+
+    def active_params(self, model, P, stream):
+        """(block, pos): the list-order copy of the parameters the LM chains load per Gaussian (gslm_active_params)
+        for active_list(), and the inverse map pos [P] (list row of a Gaussian, -1 off the list).  The block is a
+        snapshot of the leaves, so it is keyed on them: built with the list (a forward or backward drops both) and
+        again whenever a leaf was replaced or written in place since (storage address and version counter), which
+        is checked here at every use -- a solve never reads a block older than its parameters."""
+        ids, na = self.active_list(P, stream)
+        leaves = (model._xyz, model._scaling, model._rotation, model._opacity)
+        key = tuple((t.data_ptr(), t._version) for t in leaves)
+        if self._params is None or self._params[0] != key:
+            dev = self.device
+            block = _lib.u8(lib.gslm_active_params_bytes(na), dev)
+            pos = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+            g = raw_gaussians(model)
+            check(lib.gslm_active_params(ctypes.byref(g), self.geom.data_ptr(), P, ids.data_ptr() if na else None, na,
+                                         block.data_ptr(), block.numel(), pos.data_ptr(), stream), "gslm_active_params")
+            self._params = (key, block, pos)
+        return self._params[1], self._params[2]
 
     def forward(self, g, stream, want_invdepth=True):
         """The full forward (the drop-in's gslm_preprocess + gslm_rasterize).  want_invdepth=False: the LM paths,
@@ -364,9 +386,11 @@ class LMProblem:
                                  exposure_zero=exposure_zero, cg_ctl=cg_ctl)
         return fuse
 
-    def local_normal_matvec(self, v, y, damp=False, dot_out=None, pre=None, exposure_zero=False, cg_ctl=None):
+    def local_normal_matvec(self, v, y, damp=False, dot_out=None, pre=None, exposure_zero=False, cg_ctl=None,
+                            lean=None):
         """y = [D v +] sum over this problem's views of 2 J_b^T W_b J_b v  (overwrites y).
-        pre, exposure_zero, cg_ctl: see matvec_dot."""
+        pre, exposure_zero, cg_ctl: see matvec_dot.  lean: a GslmCgLean for an active_view()'s one product
+        (_cgls_lean: GSLM_MV_LEAN)."""
         g = raw_gaussians(self.model)
         vs = self.layout.grads_struct(v)
         ys = self.layout.grads_struct(y)
@@ -392,10 +416,13 @@ class LMProblem:
                 opts.dot_vy = dot_out
                 opts.dot_scratch = self.dot_scratch.data_ptr()
                 opts.dot_scratch_bytes = self.dot_scratch.numel() * 8
+            if lean is not None and lean.dot_defer:  # <v, y> stays as the gather's partials in dot_scratch
+                opts.dot_scratch = self.dot_scratch.data_ptr()
+                opts.dot_scratch_bytes = self.dot_scratch.numel() * 8
             if self.ssim:
                 self._ssim_product(b, vr, g, vs, ys, opts)
                 continue
-            self._view_product(vr, g, vs, self.weights[b].data_ptr(), ys, opts, "gslm_matvec_view_ex")
+            self._view_product(vr, g, vs, self.weights[b].data_ptr(), ys, opts, "gslm_matvec_view_ex", lean=lean)
             vr.tail_clean = True
         if exposure_zero:
             pass  # y[e0:e1] = D v[e0:e1] = 0 already (matvec_dot)
@@ -405,9 +432,15 @@ class LMProblem:
             y[e0:e1].zero_()
         return y
 
-    def _view_product(self, vr, g, vs, weight, ys, opts, what):
+    def _view_product(self, vr, g, vs, weight, ys, opts, what, lean=None):
         """gslm_matvec_view_ex on one view -- or, on an active_view() (v and y hold the listed Gaussians only),
-        gslm_matvec_view_active."""
+        gslm_matvec_view_active (with the lean loop's options when lean is given)."""
+        if lean is not None:  # the options extended by the lean loop's (GSLM_MV_LEAN)
+            ext = _lib.GslmMatvecOptsLean()
+            ctypes.memmove(ctypes.addressof(ext.base), ctypes.addressof(opts), ctypes.sizeof(opts))
+            ext.base.flags |= MV_LEAN
+            ext.lean = lean
+            opts = ext
         if self._active is not None:
             ids, na = self._active
             check(lib.gslm_matvec_view_active(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(vs), weight,
@@ -932,6 +965,92 @@ def _active_view_for(prob, g, callback):
     return act
 
 
+def _lean_applies(act, check_every, max_iter):
+    """Whether cgls_fused's solve on the active view `act` takes the lean loop (_cgls_lean): benchmark mode (no
+    stopping tests), the plain residual, scalars that stay on this device.  GSLM_CG_LEAN=0 keeps the loop below (the switch exists for A/B runs)."""
+    return (not check_every and max_iter >= 1 and not act.ssim and getattr(act, "allreduce_scalars", None) is None
+            and os.environ.get("GSLM_CG_LEAN", "1") != "0")
+
+
+def _cgls_lean(prob, act, g, max_iter, restart_iter):
+    """cgls_fused's benchmark-mode loop on an active view with less work around the tile pass (DESIGN.md 4.5a.1);
+    x is bitwise that loop's.  Per iteration: tangent (with p = s + beta p and the deferred x += alpha p), tile
+    pass, gather, update -- no finalising launch: the gather leaves delta and the update leaves gamma' as block
+    partials, and the kernel that needs the scalar sums them (the update: delta, and after a start gamma_0; the next
+    tangent kernel: gamma'; the solve's last launch: the last gamma'), one of its blocks storing the sum to the
+    scalar's slot of sc.  The per-Gaussian kernels read the chains' parameters from the view's list-order block.
+    One launch starts the solve from the full-layout g and one ends it in the full-layout x.  A restart
+    (restart_iter < max_iter) runs cgls_fused's own flush -> matvec -> dot sequence on the packed g."""
+    full = act._full
+    vr = act.views[0]
+    ids, Pa = act._active
+    n = act.layout.numel
+    dev, st = act.device, act.stream
+    P = full.layout.P
+    lo = (3 * Pa // 4) * 4  # (mask_xyz: the xyz group is zero in every iterate, as in cgls_fused)
+    na = n - lo
+    w, ng, tail = act._pack_args()
+    block, pos = vr.active_params(act.model, P, st)
+    sc = torch.zeros(16, dtype=torch.float64, device=dev)
+    ptr = lambda i: sc.data_ptr() + 8 * i
+    off = lambda t: t.data_ptr() + 4 * lo
+    GAM, GAMN, DEL = 0, 1, 2
+    NB = 1024  # DOT_BLOCKS: partials of a flat-vector dot
+    x, s, p, q = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(4))
+    part_g0 = torch.empty(NB, dtype=torch.float64, device=dev)  # gamma_0's partials
+    part_gn = torch.empty(NB, dtype=torch.float64, device=dev)  # gamma's: not the buffer delta's are in
+    part_d = act.dot_scratch
+    npd = (Pa + 255) // 256
+    ids_ptr = ids.data_ptr() if Pa else None
+    ez = prob.exposure_is_zero(g)
+    check(lib.gslm_cg_start_active(g.data_ptr(), ids_ptr, Pa, P, w, ng, tail, lo, s.data_ptr(), p.data_ptr(),
+                                   q.data_ptr(), x.data_ptr(), part_g0.data_ptr(), st), "gslm_cg_start_active")
+    gam_part = part_g0.data_ptr()  # gamma still as partials (until the first update stores it)
+    gp = None
+    pend = pre = None
+    iter_total = 0
+    first = True
+    while iter_total < max_iter:
+        if not first:
+            check(lib.gslm_axpy_dev(na, pend[0], pend[1], 1.0, off(p), off(x), st), "gslm_axpy_dev")
+            pend = pre = None
+            if gp is None:
+                gp = act.pack(g)
+            act.matvec(x, q)
+            torch.sub(gp, q, out=s)
+            p.copy_(s)
+            act.dot(s[lo:], s[lo:], ptr(GAM))
+            gam_part = None
+        first = False
+        for _ in range(restart_iter):
+            lean = _lib.GslmCgLean()
+            lean.dot_defer = 1
+            lean.params = block.data_ptr()
+            fpre = None
+            if pre is not None:
+                fpre = pre + (x, pend[0], pend[1])
+                pend = None
+                lean.beta_partials, lean.beta_np, lean.beta_store = part_gn.data_ptr(), NB, pre[1]
+            act.local_normal_matvec(p, q, damp=True, pre=fpre, exposure_zero=ez, lean=lean)
+            check(lib.gslm_cg_update_lean(na, ptr(GAM), gam_part, NB if gam_part else 0, part_d.data_ptr(), npd,
+                                          ptr(DEL), off(p), off(q), off(s), part_gn.data_ptr(), st),
+                  "gslm_cg_update_lean")
+            gam_part = None
+            pend = (ptr(GAM), ptr(DEL))  # alpha = gamma / delta, read before either slot is rewritten
+            pre = (s, ptr(GAMN), ptr(GAM))  # beta = gamma' / gamma (gamma' stored to its slot by the kernel that sums it)
+            GAM, GAMN = GAMN, GAM
+            iter_total += 1
+            if iter_total >= max_iter:
+                break
+    out = torch.empty(full.layout.numel, dtype=torch.float32, device=dev)
+    check(lib.gslm_cg_end_active(x.data_ptr(), p.data_ptr(), pend[0], pend[1], lo, pos.data_ptr(), Pa, P, w, ng, tail,
+                                 out.data_ptr(), part_gn.data_ptr(), NB, ptr(GAM), st), "gslm_cg_end_active")
+    # what the solve left on the device (tests/test_gpu_cg_lean.py): the scalar slots and the partials behind them
+    act._full._lean_state = {"sc": sc, "gamma": GAM, "delta": DEL, "gamma_partials": part_gn,
+                             "delta_partials": part_d[:npd], "s": s, "p": p, "q": q, "lo": lo}
+    return out, {"iters": iter_total, "residuals": []}
+
+
 def cgls_fused(prob, g, max_iter=10, restart_iter=10, tol=1e-10, atol=0.0, check_every=True, verbose=False,
                callback=None, host_checks=None):
     """cgls_damped (conjugate_gradient.py:51-127) on the fused operator, x0 = 0.
@@ -947,9 +1066,12 @@ def cgls_fused(prob, g, max_iter=10, restart_iter=10, tol=1e-10, atol=0.0, check
     A local single-view problem with the xyz mask is solved on the Gaussians its view can move (LMProblem.
     active_view: the rows of every CG vector that are exactly zero throughout are left out of the vectors, so the
     per-Gaussian kernels stream Pa rows instead of P); x comes back in the full layout.  GSLM_CG_ACTIVE=0 keeps
-    the full vectors.  Not taken with a callback (it sees the solver's own vectors), for several views or the
+    the full vectors.  In benchmark mode that solve runs _cgls_lean's loop (same iterates bitwise, fewer launches;
+    GSLM_CG_LEAN=0 keeps this function's).  Not taken with a callback (it sees the solver's own vectors), for several views or the
     Gaussian-sharded operators."""
     act = _active_view_for(prob, g, callback)
+    if act is not None and _lean_applies(act, check_every, max_iter):
+        return _cgls_lean(prob, act, g, max_iter, restart_iter)
     if act is not None:
         gp = act.pack(g)
         if prob.exposure_is_zero(g):

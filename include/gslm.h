@@ -374,6 +374,55 @@ int gslm_active_pack(const float* src, float* dst, const int32_t* active_ids, in
 int gslm_active_unpack(const float* src, float* dst, const int32_t* active_ids, int64_t n_active, int64_t P,
                        const int32_t* widths, int32_t ngroups, int64_t tail_n, void* stream);
 
+/* ---- The lean single-view CG loop (additive entry points, still ABI 9) ----
+ * The benchmark-mode solve on an active list with less work around the tile pass and bitwise the same iterates:
+ *  - a dot's block partials are summed by the kernel that needs the scalar (the additions of gslm_dot_finalize in
+ *    its order), so the loop launches no finalisation; one consumer also stores the sum to the scalar's slot;
+ *  - the per-Gaussian kernels read the chains' parameters from a copy in list order (gslm_active_params);
+ *  - one launch starts a solve (gslm_cg_start_active) and one ends it (gslm_cg_end_active). */
+typedef struct gslm_cg_lean {
+  const void* beta_partials; /* beta_num of the fused direction update (gslm_matvec_opts.xpby_s) as the beta_np
+                                partials gslm_cg_update_lean left, or NULL: *beta_num is finished.  Not dot_scratch. */
+  int32_t beta_np;
+  int32_t dot_defer;         /* nonzero: GATHER leaves <v, y> as (n_active + 255) / 256 partials in
+                                opts->dot_scratch and launches no finalisation (opts->dot_vy must be NULL) */
+  double* beta_store;        /* or NULL: receives the sum of beta_partials */
+  const void* params;        /* or NULL: gslm_active_params' block for active_ids */
+} gslm_cg_lean;
+/* gslm_matvec_view_active takes them as an extension of its options: with GSLM_MV_LEAN in opts->flags, opts points
+ * to the base member of a gslm_matvec_opts_lean. */
+#define GSLM_MV_LEAN 4
+typedef struct gslm_matvec_opts_lean {
+  gslm_matvec_opts base;
+  gslm_cg_lean lean;
+} gslm_matvec_opts_lean;
+/* The parameters the LM chains load per Gaussian (xyz, raw scale, raw rotation, raw opacity, the clamp word of
+ * geom) copied in list order into block (>= gslm_active_params_bytes(n_active)), and pos_dev [P]: pos[active_ids[j]]
+ * = j, -1 for a Gaussian off the list.  The block is a snapshot: rebuild it when the list or a parameter changes. */
+size_t gslm_active_params_bytes(int64_t n_active);
+int gslm_active_params(const gslm_gaussians* g, const void* geom, int64_t P, const int32_t* active_ids,
+                       int64_t n_active, void* block, size_t block_bytes, int32_t* pos_dev, void* stream);
+/* Start of a solve on the list layout (groups as gslm_active_pack): s = p = the listed rows of the full-layout
+ * g_full, q = x = 0 (the head [0, lo) zero in all four), and partials (1024 doubles) of <s, s> over [lo, n) whose
+ * gslm_dot_finalize sum is bitwise gslm_dot's. */
+int gslm_cg_start_active(const float* g_full, const int32_t* active_ids, int64_t n_active, int64_t P,
+                         const int32_t* widths, int32_t ngroups, int64_t tail_n, int64_t lo, float* s, float* p,
+                         float* q, float* x, void* partials, void* stream);
+/* gslm_cg_update with x == NULL whose delta arrives as del_np partials (summed by every block, stored to del_dev
+ * by one), and gamma as the finished *gam_dev or -- gam_partials non-NULL, after gslm_cg_start_active -- as gam_np
+ * partials whose sum one block stores to *gam_dev; the partials of <s, s> stay in partials_out (1024 doubles, a
+ * buffer of its own). */
+int gslm_cg_update_lean(int64_t n, double* gam_dev, const void* gam_partials, int32_t gam_np,
+                        const void* del_partials, int32_t del_np, double* del_dev, const float* p, const float* q,
+                        float* s, void* partials_out, void* stream);
+/* End of a solve: out_full (full layout) = the list-layout x [+ (num / den) p on [lo, n), num_dev non-NULL] at the
+ * listed rows and the tail, +0.0f elsewhere -- gslm_axpy_dev then gslm_active_unpack in one pass over out_full;
+ * pos_dev from gslm_active_params.  fin_partials (or NULL): fin_np partials whose sum is stored to *fin_dev. */
+int gslm_cg_end_active(const float* x, const float* p, const double* num_dev, const double* den_dev, int64_t lo,
+                       const int32_t* pos_dev, int64_t n_active, int64_t P, const int32_t* widths, int32_t ngroups,
+                       int64_t tail_n, float* out_full, const void* fin_partials, int32_t fin_np, double* fin_dev,
+                       void* stream);
+
 /* ---- view-sharded exchange (multi-GPU LM product), SURVEY 8(e) ----
  * Instead of all-reducing the param-space partial J^T W J v (F = 59 floats per Gaussian at SH 3),
  * every rank all-gathers per-view screen-space sums (8 floats per Gaussian per view) and applies the
