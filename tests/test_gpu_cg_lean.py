@@ -12,7 +12,10 @@ view, a tenth of the Gaussians behind the camera, vector lengths odd: no multipl
   * the parameter block equals the scene arrays indexed by the list, and the inverse map inverts the list;
   * after the parameters change and evaluate() runs again, the next solve equals a fresh problem's bitwise;
   * the checked loop (check_every=True), which the lean path leaves alone, agrees with the full-layout loop.
-The scene, J^T b and each reference solve are computed once per module."""
+The first and the second point are repeated on the layouts that scene does not have (LAYOUT_SCENES): the full SH-rest
+group at SH 3 and SH 1 (45 and 9 floats per row, LMProblem's default sh_projection=False), SH 0 (a rest group of
+width 0), a list that holds every Gaussian, and one shorter than a block of the per-Gaussian kernels.
+The scenes, J^T b and each reference solve are computed once per module."""
 import functools
 import math
 
@@ -35,7 +38,7 @@ def _camera():
     return orbit_cameras(1, W, H, seed=1, images=[img])[0]
 
 
-def _model(cam, seed=0):
+def _model(cam, seed=0, P=P, SH=SH):
     gen = torch.Generator().manual_seed(100 + seed)
     m = synthetic_gaussians(P, SH, seed=seed, s0=0.03)
     # a tenth of the Gaussians behind the camera (culled by the near plane): Pa < P
@@ -47,9 +50,9 @@ def _model(cam, seed=0):
     return m
 
 
-def _problem(model, cam):
+def _problem(model, cam, sh_projection="auto"):
     from gslm.lm import LMProblem
-    prob = LMProblem(model, [cam], torch.zeros(3), device=DEV, sh_projection="auto")
+    prob = LMProblem(model, [cam], torch.zeros(3), device=DEV, sh_projection=sh_projection)
     prob.evaluate()
     g = prob.rhs(prob.zeros())  # builds the row map
     return prob, g
@@ -231,3 +234,100 @@ def test_checked_loop_is_unchanged(host_checks, monkeypatch):
     b2 = float(s.prob.loss)
     tol = 1e-11 * (b2 + 2.0 * float(xf.double().norm()) * float(s.g.double().norm()))
     np.testing.assert_allclose(ina["residuals"], inf["residuals"], rtol=0, atol=tol)
+
+
+# ------------------------------------------------------------------------------------------------ the other layouts
+# name -> (P, SH degree, sh_projection, kind).  "tenth_behind": _model's scene (a tenth of the Gaussians culled by the
+# near plane); "all_listed": a few translucent Gaussians in the middle of the frustum, each a pixel or more wide, so
+# every one of them blends somewhere and no pixel saturates.
+LAYOUT_SCENES = {
+    "sh3_full": (3001, 3, False, "tenth_behind"),        # rest group 45 wide: the generic-width paths
+    "sh1_full": (3001, 1, False, "tenth_behind"),        # 9 wide
+    "sh0": (3001, 0, "auto", "tenth_behind"),            # 0 wide: two groups start at the same offset
+    "all_listed_sh2_full": (300, 2, False, "all_listed"),  # Pa = P: the inverse map has no -1; 24 wide
+    "short_list_sh3": (200, 3, "auto", "tenth_behind"),  # Pa < 256: one block, one delta partial
+}
+LAYOUT_CASES = [(1, 1), (3, 2), (10, 10)]
+
+
+def _model_all_listed(P, sh, seed=0):
+    from gslm.model import inverse_sigmoid
+    gen = torch.Generator().manual_seed(200 + seed)
+    m = synthetic_gaussians(P, sh, seed=seed, s0=0.05)
+    m._xyz.data[:] = torch.rand(P, 3, generator=gen) - 0.5
+    m._opacity.data[:] = inverse_sigmoid(0.1 + 0.2 * torch.rand(P, 1, generator=gen))
+    return m
+
+
+class LayoutScene:
+    def __init__(self, name):
+        self.P, self.sh, proj, kind = LAYOUT_SCENES[name]
+        self.cam = _camera().to(DEV)
+        if kind == "tenth_behind":
+            model = _model(_camera(), P=self.P, SH=self.sh)
+        else:
+            model = _model_all_listed(self.P, self.sh)
+        self.model = model.to(DEV)
+        self.prob, self.g = _problem(self.model, self.cam, sh_projection=proj)
+        self.ids, self.Pa = self.prob.views[0].active_list(self.P, self.prob.stream)
+        self.ref = {}
+        torch.cuda.synchronize()
+
+
+@functools.lru_cache(maxsize=None)
+def layout_scene(name):
+    return LayoutScene(name)
+
+
+@pytest.mark.parametrize("name", list(LAYOUT_SCENES))
+def test_layout_scene_shapes(name):
+    s = layout_scene(name)
+    lay = s.prob.layout
+    act = s.prob.active_view()
+    w, ng, tail = act._pack_args()
+    print(f"{name}: P {s.P}  Pa {s.Pa}  N {s.prob.views[0].N}  layout {lay.numel}  active layout {act.layout.numel}  "
+          f"widths {list(w)}")
+    K = (s.sh + 1) ** 2
+    assert list(w) == [3, 3, {"sh0": 0, "short_list_sh3": 3}.get(name, 3 * (K - 1)), 3, 4, 1] and tail == 12
+    assert lay.rest_projected == (name == "short_list_sh3")
+    if name == "all_listed_sh2_full":
+        assert s.Pa == s.P and torch.equal(s.ids.cpu(), torch.arange(s.P, dtype=torch.int32))
+    elif name == "short_list_sh3":
+        assert 0 < s.Pa < min(s.P, 256)
+    else:
+        assert 256 < s.Pa < s.P
+
+
+@pytest.mark.parametrize("case", LAYOUT_CASES, ids=lambda c: f"iter{c[0]}_restart{c[1]}")
+@pytest.mark.parametrize("name", list(LAYOUT_SCENES))
+def test_x_is_bitwise_the_full_layout_loops_on_every_layout(name, case, monkeypatch):
+    """test_x_is_bitwise_the_full_layout_loops and the bitwise half of test_scalar_slots_hold_the_finalised_partials
+    on LAYOUT_SCENES."""
+    from gslm import _lib
+    s = layout_scene(name)
+    kw = dict(max_iter=case[0], restart_iter=case[1], check_every=False)
+    if case not in s.ref:
+        s.ref[case] = _solve(s.prob, s.g, monkeypatch, active=False, **kw)[0].clone()
+        assert s.prob._lean_state is None
+    ref = s.ref[case]
+    x, info = _solve(s.prob, s.g, monkeypatch, **kw)
+    st = s.prob._lean_state
+    assert st is not None, "the lean loop was not taken"
+    assert info["iters"] == case[0]
+    d = float((x.double() - ref.double()).abs().max())
+    print(f"{name} {case}: max |x| {float(ref.abs().max()):.4e}  max |x - full-layout x| {d:.3e}")
+    assert x.shape == ref.shape and torch.equal(x.view(torch.int32), ref.view(torch.int32))
+    # the gamma and delta slots: what gslm_dot_finalize makes of the partials behind them
+    out = torch.zeros(2, dtype=torch.float64, device=DEV)
+    for k, slot_name in enumerate(("gamma", "delta")):
+        part = st[slot_name + "_partials"]
+        _lib.check(_lib.lib.gslm_dot_finalize(part.data_ptr(), part.numel(), out.data_ptr() + 8 * k, s.prob.stream))
+    torch.cuda.synchronize()
+    assert st["delta_partials"].numel() == (s.Pa + 255) // 256
+    for k, slot_name in enumerate(("gamma", "delta")):
+        slot, fin = float(st["sc"][st[slot_name]]), float(out[k])
+        print(f"{name} {case} {slot_name}: slot {slot!r} finalised {fin!r}")
+        assert np.float64(slot).view(np.int64) == np.float64(fin).view(np.int64)
+    xa, _ = _solve(s.prob, s.g, monkeypatch, lean=False, **kw)
+    assert s.prob._lean_state is None
+    assert torch.equal(x.view(torch.int32), xa.view(torch.int32))
