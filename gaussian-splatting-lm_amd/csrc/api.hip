@@ -1,6 +1,7 @@
 // api.hip -- extern "C" entry points of libgslm.so (declared in include/gslm.h).
 #include <cstring>
 #include <string>
+#include <vector>
 #include "gslm_kernels.hpp"
 
 namespace gslm {
@@ -1000,6 +1001,43 @@ int gslm_active_list(const void* geom, int64_t P, int64_t N, const void* scratch
   return launch_active_list(P, N, gb, sb, flags, tmp, total, ids_dev, rows_dev, count_dev, (hipStream_t)stream);
 }
 
+size_t gslm_active_union_bytes(int64_t P) { return active_work_layout(P, nullptr, nullptr, nullptr, nullptr); }
+
+int gslm_active_union(const gslm_view_ws* ws, int32_t nviews, int64_t P, void* work, size_t work_bytes, int32_t* ids_dev,
+                      uint32_t* hrow_dev, uint32_t* aflags_dev, int64_t* count_dev, void* stream) {
+  if (!ws || nviews < 1 || P < 0 || P > MAX_P || !work || !count_dev || !hrow_dev || (P > 0 && (!ids_dev || !aflags_dev))) {
+    set_error("active_union: NULL argument, nviews below 1 or P out of range");
+    return GSLM_ERR_INVALID;
+  }
+  for (int b = 0; b < nviews; ++b)
+    if (ws[b].num_rendered < 0 || (ws[b].num_rendered > 0 && P > 0 && (!ws[b].geom || !ws[b].scratch))) {
+      set_error("active_union: negative num_rendered or a NULL workspace of a view that rendered");
+      return GSLM_ERR_INVALID;
+    }
+  if (work_bytes < gslm_active_union_bytes(P)) {
+    set_error("active_union: work area below gslm_active_union_bytes(P)");
+    return GSLM_ERR_CAPACITY;
+  }
+  for (int b = 0; b < nviews; ++b)
+    if (ws[b].num_rendered > 0 && ws[b].scratch_bytes < gslm_scratch_bytes(P, ws[b].num_rendered)) {
+      set_error("active_union: scratch workspace too small");
+      return GSLM_ERR_CAPACITY;
+    }
+  std::vector<GeomBufs> gbs(nviews);
+  std::vector<ScratchBufs> sbs(nviews);
+  std::vector<int64_t> nr(nviews);
+  for (int b = 0; b < nviews; ++b) {
+    nr[b] = ws[b].num_rendered;
+    if (nr[b] == 0) continue;  // nothing rendered: no row map exists, the workspaces are not read
+    geom_layout(P, const_cast<void*>(ws[b].geom), &gbs[b]);
+    scratch_layout(P, nr[b], const_cast<void*>(ws[b].scratch), &sbs[b]);
+  }
+  uint32_t *flags, *tmp, *total;
+  active_work_layout(P, work, &flags, &tmp, &total);
+  return launch_active_union(gbs.data(), sbs.data(), nr.data(), nviews, P, flags, tmp, total, ids_dev, hrow_dev,
+                             aflags_dev, count_dev, (hipStream_t)stream);
+}
+
 int gslm_inspect_rowmap(const void* geom, int64_t P, int64_t N, const void* scratch, size_t scratch_bytes,
                         uint32_t* goff, uint32_t* hscan, void* stream) {
   if (P < 0 || N < 0 || !geom || !scratch) { set_error("inspect_rowmap: NULL workspace or negative size"); return GSLM_ERR_INVALID; }
@@ -1140,10 +1178,19 @@ int gslm_gather_screen(const gslm_view* views, int32_t nviews, const gslm_gaussi
   return GSLM_OK;
 }
 
-int gslm_gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t nviews, const gslm_gaussians* gi,
-                      const gslm_grads* vin, const gslm_grads* y, const gslm_matvec_opts* opts, void* stream) {
+// gslm_gather_views (na < 0) and gslm_gather_views_active (na >= 0: the groups of vin and y hold the na Gaussians
+// ids[0 .. na) of the batch's union list only)
+static int gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t nviews, const gslm_gaussians* gi,
+                        const gslm_grads* vin, const gslm_grads* y, const gslm_matvec_opts* opts, const int32_t* ids,
+                        int64_t na, const uint32_t* hrow, int64_t hstride, const uint32_t* aflags, int64_t fstride,
+                        void* stream) {
+  const bool active = na >= 0;
   if (!views || !ws || nviews < 1 || nviews > MAX_SCREEN_VIEWS || !gi || !vin || !y) {
     set_error("gather_views: NULL argument or nviews outside 1..16");
+    return GSLM_ERR_INVALID;
+  }
+  if (active && (na > gi->P || !hrow || hstride < na + 1 || fstride < na || (na > 0 && (!ids || !aflags)))) {
+    set_error("gather_views_active: n_active above P, a NULL list or a stride that does not hold it");
     return GSLM_ERR_INVALID;
   }
   ViewK vk[MAX_SCREEN_VIEWS];
@@ -1175,7 +1222,7 @@ int gslm_gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t nv
   const int32_t stages = (opts && opts->stages) ? opts->stages : GSLM_STAGE_ALL;
   const double* damp7 = opts ? opts->damp7 : nullptr;
   double* dot_out = opts ? opts->dot_vy : nullptr;
-  if (dot_out && (!opts->dot_scratch || opts->dot_scratch_bytes < gslm_dot_scratch_bytes(g.P))) {
+  if (dot_out && (!opts->dot_scratch || opts->dot_scratch_bytes < gslm_dot_scratch_bytes(active ? na : g.P))) {
     set_error("gather_views: dot scratch too small");
     return GSLM_ERR_CAPACITY;
   }
@@ -1183,9 +1230,24 @@ int gslm_gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t nv
   RestK rc;
   if ((st = rest_opts("gather_views", opts, nviews, &rc))) return st;
   if ((st = launch_gather_views(vk, gbs, sbs, nr, nviews, g, make_gradk(y), make_gradk(vin), damp7,
-                                (stages & GSLM_STAGE_OVERWRITE) != 0, part, dot_out, (hipStream_t)stream, rc)))
+                                (stages & GSLM_STAGE_OVERWRITE) != 0, part, dot_out, (hipStream_t)stream, rc, ids,
+                                active ? na : -1, hrow, hstride, aflags, fstride)))
     return st;
   return GSLM_OK;
+}
+
+int gslm_gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t nviews, const gslm_gaussians* gi,
+                      const gslm_grads* vin, const gslm_grads* y, const gslm_matvec_opts* opts, void* stream) {
+  return gather_views(views, ws, nviews, gi, vin, y, opts, nullptr, -1, nullptr, 0, nullptr, 0, stream);
+}
+
+int gslm_gather_views_active(const gslm_view* views, const gslm_view_ws* ws, int32_t nviews, const gslm_gaussians* gi,
+                             const gslm_grads* vin, const gslm_grads* y, const int32_t* active_ids, int64_t n_active,
+                             const uint32_t* hrow, int64_t hrow_stride, const uint32_t* aflags, int64_t flags_stride,
+                             const gslm_matvec_opts* opts, void* stream) {
+  if (n_active < 0) { set_error("gather_views_active: negative n_active"); return GSLM_ERR_INVALID; }
+  return gather_views(views, ws, nviews, gi, vin, y, opts, active_ids, n_active, hrow, hrow_stride, aflags,
+                      flags_stride, stream);
 }
 
 int gslm_view_flags(const void* geom, int64_t P, uint32_t* out, void* stream) {
@@ -1195,11 +1257,19 @@ int gslm_view_flags(const void* geom, int64_t P, uint32_t* out, void* stream) {
   return launch_view_flags(P, gb, out, (hipStream_t)stream);
 }
 
-int gslm_tangent_views(const gslm_view* views, int32_t nviews, const gslm_gaussians* gi, const gslm_grads* vin,
-                       int32_t mask_xyz, const uint32_t* vflags, int64_t flags_stride, float* trec_out,
-                       int64_t trec_stride, const gslm_matvec_opts* opts, void* stream) {
+// gslm_tangent_views (na < 0) and gslm_tangent_views_active (na >= 0: the groups of vin and of the fused direction
+// update, and the rows of vflags, hold the na Gaussians ids[0 .. na) of the batch's union list only)
+static int tangent_views(const gslm_view* views, int32_t nviews, const gslm_gaussians* gi, const gslm_grads* vin,
+                         int32_t mask_xyz, const uint32_t* vflags, int64_t flags_stride, float* trec_out,
+                         int64_t trec_stride, const gslm_matvec_opts* opts, const int32_t* ids, int64_t na,
+                         void* stream) {
+  const bool active = na >= 0;
   if (!views || nviews < 1 || nviews > MAX_SCREEN_VIEWS || !gi || !vin) {
     set_error("tangent_views: NULL argument or nviews outside 1..16");
+    return GSLM_ERR_INVALID;
+  }
+  if (active && (!mask_xyz || na > gi->P || (na > 0 && !ids))) {
+    set_error("tangent_views_active: the LM rows (mask_xyz) and a list of at most P Gaussians");
     return GSLM_ERR_INVALID;
   }
   ViewK vk[MAX_SCREEN_VIEWS];
@@ -1214,7 +1284,7 @@ int gslm_tangent_views(const gslm_view* views, int32_t nviews, const gslm_gaussi
     set_error("tangent_views: gaussians must be the raw GaussianModel leaves (raw = 1)");
     return GSLM_ERR_INVALID;
   }
-  if (g.P > 0 && (!vflags || !trec_out || flags_stride < g.P || trec_stride < g.P)) {
+  if (g.P > 0 && (!vflags || !trec_out || flags_stride < (active ? na : g.P) || trec_stride < g.P)) {
     set_error("tangent_views: NULL vflags / trec_out or a stride below P");
     return GSLM_ERR_INVALID;
   }
@@ -1235,7 +1305,23 @@ int gslm_tangent_views(const gslm_view* views, int32_t nviews, const gslm_gaussi
   const bool fused = opts && opts->xpby_s;
   if (fused && (st = build_xpby(opts, vin, R, mask_xyz != 0, &xp))) return st;
   return launch_tangent_views(vk, nviews, g, t, vflags, flags_stride, trec_out, trec_stride, fused ? &xp : nullptr,
-                              (hipStream_t)stream, mask_xyz != 0, rc.view_base);
+                              (hipStream_t)stream, mask_xyz != 0, rc.view_base, ids, active ? na : -1);
+}
+
+int gslm_tangent_views(const gslm_view* views, int32_t nviews, const gslm_gaussians* gi, const gslm_grads* vin,
+                       int32_t mask_xyz, const uint32_t* vflags, int64_t flags_stride, float* trec_out,
+                       int64_t trec_stride, const gslm_matvec_opts* opts, void* stream) {
+  return tangent_views(views, nviews, gi, vin, mask_xyz, vflags, flags_stride, trec_out, trec_stride, opts, nullptr, -1,
+                       stream);
+}
+
+int gslm_tangent_views_active(const gslm_view* views, int32_t nviews, const gslm_gaussians* gi, const gslm_grads* vin,
+                              int32_t mask_xyz, const int32_t* active_ids, int64_t n_active, const uint32_t* aflags,
+                              int64_t flags_stride, float* trec_out, int64_t trec_stride, const gslm_matvec_opts* opts,
+                              void* stream) {
+  if (n_active < 0) { set_error("tangent_views_active: negative n_active"); return GSLM_ERR_INVALID; }
+  return tangent_views(views, nviews, gi, vin, mask_xyz, aflags, flags_stride, trec_out, trec_stride, opts, active_ids,
+                       n_active, stream);
 }
 
 int gslm_matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gslm_grads* vin,

@@ -713,6 +713,99 @@ int launch_active_list(int64_t P, int64_t N, const GeomBufs& gb, const ScratchBu
   return GSLM_OK;
 }
 
+// ---- the union list of a view batch (gslm_active_union), once per geometry ----
+// Up to MAX_SCREEN_VIEWS views' row maps per launch; tiles NULL: the view rendered nothing (no row map exists).
+// Every view's geometry has the layout of the same P, so goff and clampw lie at one offset from tiles in all of them.
+struct UnionWsK {
+  const uint32_t* tiles[MAX_SCREEN_VIEWS];
+  const uint32_t* hscan[MAX_SCREEN_VIEWS];
+  int64_t N[MAX_SCREEN_VIEWS];
+  int32_t goff_off, clamp_off;  // in words, from tiles
+  int n;
+};
+
+// flags[i] = [flags[i] |] (Gaussian i owns a head row in one of these views)
+__global__ __launch_bounds__(256) void k_union_flags(int64_t P, UnionWsK ws, int first, uint32_t* __restrict__ flags) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= P) return;
+  uint32_t f = first ? 0u : flags[i];
+  for (int b = 0; b < ws.n && !f; ++b)
+    if (ws.tiles[b]) f = owns_head_row(i, ws.tiles[b], ws.tiles[b] + ws.goff_off, ws.hscan[b]);
+  flags[i] = f;
+}
+
+// pos = the exclusive scan of the union flags, so Gaussian i is listed when pos steps at i (pos[P] being *total):
+// ids[pos[i]] = i, and for view b = view_base + k of this launch hrow[b][pos[i]] = hscan_b[goff_b[i]] -- the first
+// head row of i in view b, or of the next Gaussian that has one: the Gaussians between two listed ones own no row in
+// any view, so entry j's rows in view b are [hrow[b][j], hrow[b][j + 1]), empty when view b does not move it --
+// hrow[b][*total] = view b's head rows, and aflags[b][pos[i]] = k_view_flags' word of i in view b.  A view without
+// a row map gets zeros.  The launch with view_base 0 also writes ids and *count.
+__global__ __launch_bounds__(256) void k_union_scatter(int64_t P, UnionWsK ws, int view_base,
+                                                        const uint32_t* __restrict__ pos,
+                                                        const uint32_t* __restrict__ total, int32_t* __restrict__ ids,
+                                                        uint32_t* __restrict__ hrow, uint32_t* __restrict__ aflags,
+                                                        int64_t* __restrict__ count) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t na = *total;
+  if (i == 0) {
+    if (view_base == 0) *count = (int64_t)na;
+    for (int b = 0; b < ws.n; ++b)
+      hrow[(int64_t)(view_base + b) * (P + 1) + na] = ws.tiles[b] ? ws.hscan[b][ws.N[b]] : 0u;
+  }
+  if (i >= P) return;
+  const uint32_t j = pos[i];
+  if ((i + 1 < P ? pos[i + 1] : na) == j) return;  // not listed
+  if (view_base == 0) ids[j] = (int32_t)i;
+  for (int b = 0; b < ws.n; ++b) {
+    const uint32_t* __restrict__ tiles = ws.tiles[b];
+    uint32_t h = 0u, f = 0u;
+    if (tiles) {
+      h = ws.hscan[b][(tiles + ws.goff_off)[i]];
+      f = tiles[i] ? (0x80000000u | ((tiles + ws.clamp_off)[i] & 7u)) : 0u;
+    }
+    hrow[(int64_t)(view_base + b) * (P + 1) + j] = h;
+    aflags[(int64_t)(view_base + b) * P + j] = f;
+  }
+}
+
+int launch_active_union(const GeomBufs* gbs, const ScratchBufs* sbs, const int64_t* nr, int nviews, int64_t P,
+                        uint32_t* flags, uint32_t* scan_tmp, uint32_t* total, int32_t* ids, uint32_t* hrow,
+                        uint32_t* aflags, int64_t* count, hipStream_t s) {
+  if (P <= 0) {
+    GSLM_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(int64_t), s));
+    GSLM_HIP_CHECK(hipMemsetAsync(hrow, 0, (size_t)nviews * sizeof(uint32_t), s));  // [V][P + 1] with P = 0
+    return GSLM_OK;
+  }
+  const unsigned nb = (unsigned)((P + 255) / 256);
+  auto chunk = [&](int b0) {
+    UnionWsK ws{};
+    ws.n = nviews - b0 < MAX_SCREEN_VIEWS ? nviews - b0 : MAX_SCREEN_VIEWS;
+    for (int k = 0; k < ws.n; ++k) {
+      const int b = b0 + k;
+      if (nr[b] <= 0) continue;  // tiles stays NULL
+      ws.goff_off = (int32_t)(gbs[b].goff - gbs[b].tiles);
+      ws.clamp_off = (int32_t)(gbs[b].clampw - gbs[b].tiles);
+      ws.tiles[k] = gbs[b].tiles;
+      ws.hscan[k] = sbs[b].hscan;
+      ws.N[k] = nr[b];
+    }
+    return ws;
+  };
+  for (int b0 = 0; b0 < nviews; b0 += MAX_SCREEN_VIEWS) {
+    hipLaunchKernelGGL(k_union_flags, dim3(nb), dim3(256), 0, s, P, chunk(b0), b0 == 0 ? 1 : 0, flags);
+    GSLM_LAUNCH_CHECK();
+  }
+  // in place, as the row map's own scan
+  const int st = exclusive_scan_u32(flags, nullptr, flags, P, scan_tmp, total, s);
+  if (st) return st;
+  for (int b0 = 0; b0 < nviews; b0 += MAX_SCREEN_VIEWS) {
+    hipLaunchKernelGGL(k_union_scatter, dim3(nb), dim3(256), 0, s, P, chunk(b0), b0, flags, total, ids, hrow, aflags,
+                       count);
+    GSLM_LAUNCH_CHECK();
+  }
+  return GSLM_OK;
+}
+
 // ---- the line search's shared binning (gslm_union_*) ----
 // The seven line-search points of train_jvp.py:262-280 differ only in the groups the LM step moves (xyz is masked,
 // :221-227), so one view's Gaussians keep their screen centre and depth order at every point and only their

@@ -5,6 +5,7 @@
 //   y = [y +] [D v +] sum_b C_b^T (sum of Gaussian i's head rows in view b),   <v, y> partials
 // Same row sums (block_sum_rows<2> over the same 256-Gaussian partition), same chain and the same accumulation
 // order as k_rowsum_screen x V + k_gather_screen, so the results are those kernels' bit for bit.
+#include <type_traits>
 #include "gslm_gather.hpp"
 
 namespace gslm {
@@ -18,17 +19,45 @@ struct ViewWsK {
   uint32_t hoff[MAX_SCREEN_VIEWS];
   int32_t goff_off, clamp_off;  // in words, from tiles
 };
+// ACTIVE's workspace argument instead: the views' rows (NULL as above) and the union list of the batch
+// (gslm_active_union).  v and y hold the na listed Gaussians, entry j's head rows in view b are
+// [hrow[b hstride + j], hrow[b hstride + j + 1]) and aflags[b fstride + j] is that view's gslm_view_flags word of
+// Gaussian ids[j].
+struct ActiveWsK {
+  const float4* rows[MAX_SCREEN_VIEWS];
+  const int32_t* ids;
+  const uint32_t* hrow;
+  const uint32_t* aflags;
+  int64_t na, hstride, fstride;
+};
+static_assert(sizeof(ActiveWsK) <= sizeof(ViewWsK), "k_gather_views<., ACTIVE>: no more kernel arguments than the full one");
 static_assert(sizeof(ViewsK) + sizeof(ViewWsK) + sizeof(GaussK) + sizeof(FlatK) + sizeof(RestK) <= 4096,
               "k_gather_views: kernel arguments past 4 KB");
 
-template <bool COORDS>
-__global__ __launch_bounds__(256) void k_gather_views(ViewsK vs, ViewWsK ws, GaussK g, FlatK o, RestK rc) {
+template <bool ACTIVE, typename WS>
+__device__ __forceinline__ int64_t nrows_of(const WS& ws, const GaussK& g) {
+  if constexpr (ACTIVE) return ws.na;
+  else return g.P;
+}
+
+// ACTIVE (gslm_gather_views_active): thread j handles Gaussian ids[j] of the scene (parameters, the factor R) and row
+// j of v, y, hrow and aflags.  A block's 256 consecutive listed Gaussians still own one contiguous range of head rows
+// in every view -- the Gaussians between two listed ones own none in any view -- so the row sums and their order are
+// the full kernel's (k_gather_lm<..., ACTIVE> for one view); the view's tiles, goff, hscan and clampw are not read.
+template <bool COORDS, bool ACTIVE = false>
+__global__ __launch_bounds__(256) void k_gather_views(ViewsK vs, std::conditional_t<ACTIVE, ActiveWsK, ViewWsK> ws,
+                                                       GaussK g, FlatK o, RestK rc) {
   extern __shared__ __attribute__((aligned(16))) float s_rest[];  // the views' row chunks, then the epilogue's stage
   __shared__ double s_dot[4];
   if (cg_stopped(vs.v[0])) return;  // a stopped solve (gslm_matvec_opts.cg_ctl): block-uniform, before any barrier
+  const int64_t nrows = nrows_of<ACTIVE>(ws, g);  // rows of v and y
   const int64_t i0 = (int64_t)blockIdx.x * blockDim.x;
-  const int64_t i = i0 + threadIdx.x;
-  const int64_t il = i0 + min((int64_t)blockDim.x, g.P - i0) - 1;  // the block's last Gaussian
+  const int64_t j = i0 + threadIdx.x;
+  const int64_t nvalid = min((int64_t)blockDim.x, nrows - i0);
+  const int64_t il = i0 + nvalid - 1;  // the block's last Gaussian
+  const bool valid = j < nrows;
+  int64_t i = j;
+  if constexpr (ACTIVE) i = valid ? (int64_t)ws.ids[j] : 0;
   ChainOut acc;
   acc.dop = 0.f;
 #pragma unroll
@@ -41,19 +70,33 @@ __global__ __launch_bounds__(256) void k_gather_views(ViewsK vs, ViewWsK ws, Gau
   for (int b = 0; b < vs.n; ++b) {
     const float4* __restrict__ rows = ws.rows[b];
     if (!rows) continue;  // an empty view: a kernel argument, so the whole block skips it (no barrier is missed)
-    const uint32_t* __restrict__ tiles = ws.tiles[b];
-    const uint32_t* __restrict__ goff = tiles + ws.goff_off;
-    const uint32_t* __restrict__ hscan = reinterpret_cast<const uint32_t*>(rows + ws.hoff[b]);
-    // the block's contiguous head-row range of this view and this Gaussian's part of it (k_rowsum_screen); every
-    // thread runs the row sums -- they hold barriers -- also past P and for a Gaussian the view does not see
-    const uint32_t n = i < g.P ? tiles[i] : 0u;
-    const uint32_t R0 = hscan[goff[i0]], R1 = hscan[goff[il] + tiles[il]];
-    const uint32_t h0 = i < g.P ? hscan[goff[i]] : R1, h1 = i < g.P ? hscan[goff[i] + n] : R1;
     float G2[NV];
-    block_sum_rows<2>(rows, R0, R1, h0, h1 - h0, reinterpret_cast<float4*>(s_rest), G2);
-    if (!n) continue;
+    uint32_t clamp;
+    if constexpr (ACTIVE) {
+      // the list's own row offsets and flag words, read coalesced; every thread runs the row sums (they hold
+      // barriers), also past na and for a listed Gaussian this view does not move (an empty range)
+      const uint32_t* __restrict__ hrow = ws.hrow + (int64_t)b * ws.hstride;
+      const uint32_t f = valid ? ws.aflags[(int64_t)b * ws.fstride + j] : 0u;
+      const uint32_t R0 = hrow[i0], R1 = hrow[i0 + nvalid];
+      const uint32_t h0 = valid ? hrow[j] : R1, h1 = valid ? hrow[j + 1] : R1;
+      block_sum_rows<2>(rows, R0, R1, h0, h1 - h0, reinterpret_cast<float4*>(s_rest), G2);
+      if (!(f >> 31)) continue;
+      clamp = f & 7u;
+    } else {
+      const uint32_t* __restrict__ tiles = ws.tiles[b];
+      const uint32_t* __restrict__ goff = tiles + ws.goff_off;
+      const uint32_t* __restrict__ hscan = reinterpret_cast<const uint32_t*>(rows + ws.hoff[b]);
+      // the block's contiguous head-row range of this view and this Gaussian's part of it (k_rowsum_screen); every
+      // thread runs the row sums -- they hold barriers -- also past P and for a Gaussian the view does not see
+      const uint32_t n = i < g.P ? tiles[i] : 0u;
+      const uint32_t R0 = hscan[goff[i0]], R1 = hscan[goff[il] + tiles[il]];
+      const uint32_t h0 = i < g.P ? hscan[goff[i]] : R1, h1 = i < g.P ? hscan[goff[i] + n] : R1;
+      block_sum_rows<2>(rows, R0, R1, h0, h1 - h0, reinterpret_cast<float4*>(s_rest), G2);
+      if (!n) continue;
+      clamp = (tiles + ws.clamp_off)[i] & 7u;
+    }
     ChainOut co;
-    chain_vjp<true>(vs.v[b], g, i, true, (tiles + ws.clamp_off)[i] & 7u, G2, false, co);
+    chain_vjp<true>(vs.v[b], g, i, true, clamp, G2, false, co);
     acc.dop += co.dop;
 #pragma unroll
     for (int k = 0; k < 3; ++k) acc.dscale[k] += co.dscale[k];
@@ -66,11 +109,11 @@ __global__ __launch_bounds__(256) void k_gather_views(ViewsK vs, ViewWsK ws, Gau
       const int col = rc.view_base + b;
       const float* Rc = rc.R + i * rest_basis_floats(rc.V) + rest_basis_floats(col);
 #pragma unroll
-      for (int j = 0; j < MAX_REST_VIEWS; ++j)
-        if (j <= col) {
-          const float r = Rc[j];
+      for (int q = 0; q < MAX_REST_VIEWS; ++q)
+        if (q <= col) {
+          const float r = Rc[q];
 #pragma unroll
-          for (int ch = 0; ch < 3; ++ch) acc.dsh[1 + j][ch] += r * co.dres[ch];
+          for (int ch = 0; ch < 3; ++ch) acc.dsh[1 + q][ch] += r * co.dres[ch];
         }
     } else {
 #pragma unroll
@@ -81,6 +124,7 @@ __global__ __launch_bounds__(256) void k_gather_views(ViewsK vs, ViewWsK ws, Gau
       }
     }
   }
+  if constexpr (ACTIVE) g.P = ws.na;  // the epilogue writes rows j < na of y (it reads P and M of g only)
   lm_epilogue<false>(g.M, g, acc, o, s_rest, s_dot);
 }
 
@@ -101,8 +145,12 @@ __global__ __launch_bounds__(256) void k_dot_final_views(const double* __restric
 
 int launch_gather_views(const ViewK* views, const GeomBufs* gbs, const ScratchBufs* sbs, const int64_t* nr,
                         int nviews, const GaussK& g, const GradK& y, const GradK& vin, const double* damp7,
-                        bool overwrite, double* dot_part, double* dot_out, hipStream_t s, const RestK& rc) {
-  if (g.P == 0) {
+                        bool overwrite, double* dot_part, double* dot_out, hipStream_t s, const RestK& rc,
+                        const int32_t* ids, int64_t na, const uint32_t* hrow, int64_t hstride, const uint32_t* aflags,
+                        int64_t fstride) {
+  const bool active = na >= 0;
+  const int64_t nrows = active ? na : g.P;  // rows of v and y
+  if (nrows == 0) {
     if (dot_out) {  // an empty sum
       hipLaunchKernelGGL(k_dot_final_views, dim3(1), dim3(256), 0, s, dot_part, 0, dot_out, views[0].stop);
       GSLM_LAUNCH_CHECK();
@@ -114,6 +162,10 @@ int launch_gather_views(const ViewK* views, const GeomBufs* gbs, const ScratchBu
   if (st) return st;
   if (nviews < 1 || nviews > MAX_SCREEN_VIEWS) {
     set_error("gather_views: 1..16 views per call");
+    return GSLM_ERR_INVALID;
+  }
+  if (active && (!ids || !hrow || !aflags || hstride < na + 1 || fstride < na)) {
+    set_error("internal: the active-list gather needs the union list and strides that hold it");
     return GSLM_ERR_INVALID;
   }
   ViewsK vs;
@@ -135,17 +187,26 @@ int launch_gather_views(const ViewK* views, const GeomBufs* gbs, const ScratchBu
     ws.rows[b] = sbs[b].contrib;
     ws.hoff[b] = (uint32_t)(hbytes / sizeof(float4));
   }
-  const unsigned nb = (unsigned)((g.P + 255) / 256);
+  ActiveWsK aw{};
+  for (int b = 0; b < nviews; ++b) aw.rows[b] = ws.rows[b];
+  aw.ids = ids;
+  aw.hrow = hrow;
+  aw.aflags = aflags;
+  aw.na = na;
+  aw.hstride = hstride;
+  aw.fstride = fstride;
+  const unsigned nb = (unsigned)((nrows + 255) / 256);
   const size_t chunk_lds = (size_t)GATHER_CHUNK * 2 * sizeof(float4);
-  if (o.rest_V) {
-    const size_t stage = (size_t)256 * 3 * o.rest_V * sizeof(float);
-    hipLaunchKernelGGL(k_gather_views<true>, dim3(nb), dim3(256), (stage > chunk_lds ? stage : chunk_lds) + 16, s, vs,
-                       ws, g, o, rc);
-  } else {
-    const size_t stage = sh_stage_floats<false>(g.M) * sizeof(float);
-    hipLaunchKernelGGL(k_gather_views<false>, dim3(nb), dim3(256), (stage > chunk_lds ? stage : chunk_lds) + 16, s,
-                       vs, ws, g, o, rc);
-  }
+  const size_t stage = (o.rest_V ? (size_t)256 * 3 * o.rest_V : sh_stage_floats<false>(g.M)) * sizeof(float);
+  const size_t lds = (stage > chunk_lds ? stage : chunk_lds) + 16;
+  if (o.rest_V && active)
+    hipLaunchKernelGGL((k_gather_views<true, true>), dim3(nb), dim3(256), lds, s, vs, aw, g, o, rc);
+  else if (o.rest_V)
+    hipLaunchKernelGGL(k_gather_views<true>, dim3(nb), dim3(256), lds, s, vs, ws, g, o, rc);
+  else if (active)
+    hipLaunchKernelGGL((k_gather_views<false, true>), dim3(nb), dim3(256), lds, s, vs, aw, g, o, rc);
+  else
+    hipLaunchKernelGGL(k_gather_views<false>, dim3(nb), dim3(256), lds, s, vs, ws, g, o, rc);
   GSLM_LAUNCH_CHECK();
   if (dot_out) {
     hipLaunchKernelGGL(k_dot_final_views, dim3(1), dim3(256), 0, s, dot_part, (int)nb, dot_out, views[0].stop);

@@ -615,14 +615,21 @@ int launch_gather_screen(const ViewK* views, int nviews, const GaussK& g, const 
 // the dot_part partials, left alone by a stopped solve
 int launch_gather_views(const ViewK* views, const GeomBufs* gbs, const ScratchBufs* sbs, const int64_t* nr,
                         int nviews, const GaussK& g, const GradK& y, const GradK& vin, const double* damp7,
-                        bool overwrite, double* dot_part, double* dot_out, hipStream_t s, const RestK& rc = RestK{});
+                        bool overwrite, double* dot_part, double* dot_out, hipStream_t s, const RestK& rc = RestK{},
+                        const int32_t* ids = nullptr, int64_t na = -1, const uint32_t* hrow = nullptr,
+                        int64_t hstride = 0, const uint32_t* aflags = nullptr, int64_t fstride = 0);
+// the union list of a view batch (gslm_active_union): nr[b] == 0 marks a view without a row map; flags [P] doubles as
+// the scan's output, scan_tmp: scan_tmp_bytes(P), total: one word; hrow [V][P + 1], aflags [V][P]
+int launch_active_union(const GeomBufs* gbs, const ScratchBufs* sbs, const int64_t* nr, int nviews, int64_t P,
+                        uint32_t* flags, uint32_t* scan_tmp, uint32_t* total, int32_t* ids, uint32_t* hrow,
+                        uint32_t* aflags, int64_t* count, hipStream_t s);
 int launch_rest_basis(const ViewK* views, int nviews, const GaussK& g, float* R, hipStream_t s);
 int launch_rest_coords(const ViewK* views, int nviews, const GaussK& g, const float* R, int mode, const float* in,
                        int64_t in_stride, float* out, int64_t out_stride, hipStream_t s);
 int launch_view_flags(int64_t P, const GeomBufs& gb, uint32_t* out, hipStream_t s);
 int launch_tangent_views(const ViewK* views, int nviews, const GaussK& g, const GaussK& t, const uint32_t* vflags,
                          int64_t fstride, float* out, int64_t ostride, const XpbyK* xp, hipStream_t s, bool compact,
-                         int view_base = 0);
+                         int view_base = 0, const int32_t* ids = nullptr, int64_t na = -1);
 int launch_jvp(const ViewK& v, const GaussK& g, const GaussK& t, const float* m2t, const GeomBufs& gb,
                const BinBufs& bb, const ImgBufs& ib, const ScratchBufs& sb, float* out_color_t, float* out_inv_t,
                hipStream_t s);

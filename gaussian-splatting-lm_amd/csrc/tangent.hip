@@ -194,63 +194,82 @@ int launch_tangent_pre(const ViewK& v, const GaussK& g, const GaussK& t, const f
 // Gaussian-sharded exchange: the tangent render records of a Gaussian range for several views (the
 // TANGENT stage of k_preprocess_jvp, looped over views), after the optional fused direction update.
 // The block's SH-rest tangent slice is staged in LDS once and read by every view's chain.
-template <bool XPBY>
+// ACTIVE (gslm_tangent_views_active): thread j handles Gaussian ids[j] of the scene (parameters, the factor R, the
+// tangent record) and row j of the tangent's groups, of the fused direction update and of the views' flag words
+// (vflags is then the union list's aflags: [view][row]), which hold the na listed Gaussians only.  Same arithmetic
+// per Gaussian as the full-layout kernel; the records land in row ids[j] of the views' [P][8] tables.
+template <bool XPBY, bool ACTIVE = false>
 __global__ __launch_bounds__(256) void k_tangent_views(ViewsK vs, GaussK g, GaussK t, const uint32_t* __restrict__ vflags,
                                                         int64_t fstride, float4* __restrict__ out, int64_t ostride,
-                                                        XpbyK xp, int compact, int view_base) {
+                                                        XpbyK xp, int compact, int view_base,
+                                                        const int32_t* __restrict__ ids, int64_t na) {
   extern __shared__ __attribute__((aligned(16))) float s_rest[];  // [256 * 3(M-1)]
   if (cg_stopped(vs.v[0])) return;  // a stopped solve (gslm_matvec_opts.cg_ctl): block-uniform, before any barrier
-  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x;
-  const int64_t i = i0 + threadIdx.x;
+  const int64_t n = ACTIVE ? na : g.P;  // rows of the tangent's groups
+  const int64_t j0 = (int64_t)blockIdx.x * blockDim.x;
+  const int64_t j = j0 + threadIdx.x;
   if (XPBY) {
-    block_xpby(xp, g.P, s_rest);
+    block_xpby(xp, n, s_rest);
   } else if (t.rest) {
-    const int64_t len = min((int64_t)blockDim.x, g.P - i0) * t.rest_stride;
-    const float* src = t.rest + i0 * t.rest_stride;
+    const int64_t len = min((int64_t)blockDim.x, n - j0) * t.rest_stride;
+    const float* src = t.rest + j0 * t.rest_stride;
     for (int64_t e = threadIdx.x; e < len; e += blockDim.x) s_rest[e] = src[e];
   }
   __syncthreads();
   if (t.rest) {
     t.rest = s_rest;
-    t.rest_base = i0;
+    t.rest_base = j0;
   }
-  if (i >= g.P) return;
+  if (j >= n) return;
+  const int64_t i = ACTIVE ? (int64_t)ids[j] : j;
 #pragma unroll 1
   for (int b = 0; b < vs.n; ++b) {
-    const uint32_t f = vflags[(int64_t)b * fstride + i];
+    const uint32_t f = vflags[(int64_t)b * fstride + j];
     if (!(f >> 31)) continue;
     t.rest_col = view_base + b;  // SH-rest coordinates: this view's column of R
     float T2[10];
-    chain_jvp<true>(vs.v[b], g, t, nullptr, i, i, f & 7u, T2);
+    chain_jvp<true>(vs.v[b], g, t, nullptr, i, j, f & 7u, T2);
     store_trec(out, (int64_t)b * ostride + i, T2, compact != 0);
   }
 }
 
 int launch_tangent_views(const ViewK* views, int nviews, const GaussK& g, const GaussK& t, const uint32_t* vflags,
                          int64_t fstride, float* out, int64_t ostride, const XpbyK* xp, hipStream_t s, bool compact,
-                         int view_base) {
+                         int view_base, const int32_t* ids, int64_t na) {
   if (nviews < 1 || nviews > MAX_SCREEN_VIEWS) {
     set_error("tangent_views: 1..16 views per call");
     return GSLM_ERR_INVALID;
   }
-  if (g.P == 0 && !(xp && xp->tail_p)) return GSLM_OK;  // an empty shard with a tail: one block updates it
+  const bool active = na >= 0;
+  const int64_t n = active ? na : g.P;
+  if (n == 0 && !(xp && xp->tail_p)) return GSLM_OK;  // an empty shard with a tail: one block updates it
   if (xp && t.rest && (t.rest != xp->p[2] || t.rest_stride != xp->w[2])) {
     set_error("internal: fused xpby expects the tangent's SH-rest group to be p's");
+    return GSLM_ERR_INVALID;
+  }
+  if (active && na > 0 && !ids) {
+    set_error("internal: the active-list tangent needs the list");
     return GSLM_ERR_INVALID;
   }
   ViewsK vs;
   for (int b = 0; b < nviews; ++b) vs.v[b] = views[b];
   vs.n = nviews;
-  const unsigned nb = (unsigned)((g.P + 255) / 256) + (g.P == 0 ? 1u : 0u);
+  const unsigned nb = (unsigned)((n + 255) / 256) + (n == 0 ? 1u : 0u);
   const size_t lds = t.rest ? (size_t)256 * t.rest_stride * sizeof(float) : 0;
   XpbyK none{};
   float4* o = reinterpret_cast<float4*>(out);
-  if (xp)
+  if (active && xp)
+    hipLaunchKernelGGL((k_tangent_views<true, true>), dim3(nb), dim3(256), lds, s, vs, g, t, vflags, fstride, o, ostride,
+                       *xp, compact ? 1 : 0, view_base, ids, na);
+  else if (active)
+    hipLaunchKernelGGL((k_tangent_views<false, true>), dim3(nb), dim3(256), lds, s, vs, g, t, vflags, fstride, o, ostride,
+                       none, compact ? 1 : 0, view_base, ids, na);
+  else if (xp)
     hipLaunchKernelGGL(k_tangent_views<true>, dim3(nb), dim3(256), lds, s, vs, g, t, vflags, fstride, o, ostride, *xp,
-                       compact ? 1 : 0, view_base);
+                       compact ? 1 : 0, view_base, nullptr, -1);
   else
     hipLaunchKernelGGL(k_tangent_views<false>, dim3(nb), dim3(256), lds, s, vs, g, t, vflags, fstride, o, ostride, none,
-                       compact ? 1 : 0, view_base);
+                       compact ? 1 : 0, view_base, nullptr, -1);
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
 }

@@ -227,6 +227,20 @@ EXPORTS = {
     "gslm_tangent_views": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int32, ctypes.POINTER(GslmGaussians),
                                           ctypes.POINTER(GslmGrads), ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64,
                                           ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p]),
+    "gslm_active_union_bytes": (ctypes.c_size_t, [ctypes.c_int64]),
+    "gslm_active_union": (ctypes.c_int, [ctypes.POINTER(GslmViewWs), ctypes.c_int32, ctypes.c_int64, ctypes.c_void_p,
+                                         ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                         ctypes.c_void_p, ctypes.c_void_p]),
+    "gslm_tangent_views_active": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int32,
+                                                 ctypes.POINTER(GslmGaussians), ctypes.POINTER(GslmGrads),
+                                                 ctypes.c_int32, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                 ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
+                                                 ctypes.c_void_p]),
+    "gslm_gather_views_active": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.POINTER(GslmViewWs), ctypes.c_int32,
+                                                ctypes.POINTER(GslmGaussians), ctypes.POINTER(GslmGrads),
+                                                ctypes.POINTER(GslmGrads), ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_int64,
+                                                ctypes.c_void_p, ctypes.c_void_p]),
     "gslm_cg_update": (ctypes.c_int, [ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                       ctypes.c_void_p, ctypes.c_void_p]),

@@ -712,7 +712,7 @@ class BatchedLMProblem(LMProblem):
     _events = None  # stage_times: HIP events recorded between the product's stages
 
     def __init__(self, model, cams, bg, gts=None, alpha_masks=None, mask_xyz=True, damp=None, device="cuda",
-                 ssim=False, lambda_dssim=0.2, sh_projection=False):
+                 ssim=False, lambda_dssim=0.2, sh_projection=False, union_active=False):
         if not mask_xyz:
             raise ValueError("BatchedLMProblem runs on the LM rows (mask_xyz=True, train_jvp.py:221-227)")
         if ssim:
@@ -739,9 +739,53 @@ class BatchedLMProblem(LMProblem):
         self._rest_R = torch.zeros((self._rest_n + 255) // 256 * 256, dtype=torch.float32,
                                    device=device) if rv else None
         self._rest_ok = False
+        self.union_active = bool(union_active)
+        self._union = None  # (the views' epochs, ids, Pa, hrow, aflags): the union list of the current geometry
+
+    def union_list(self):
+        """(ids, Pa, hrow, aflags) of gslm_active_union: the ascending int32 ids of the Gaussians that own a head row
+        in at least one view's LM row map, their number, every view's row offsets of the list ([V][P + 1]) and every
+        view's gslm_view_flags words in list order ([V][P]).  Needs every view's row map (tail_clean: a product or
+        rhs() on this geometry); built once per geometry (one read-back), kept until a view's forward or backward."""
+        if any(not vr.tail_clean or vr.N is None for vr in self.views):
+            self._union = None  # (the list is the row maps': it lives exactly as long)
+            raise RuntimeError("union_list: a view has no current LM row map (run a product or rhs() first)")
+        key = [vr.epoch for vr in self.views]
+        if self._union is None or self._union[0] != key:
+            V, P, dev = len(self.views), self.full_layout.P, self.device
+            ids = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
+            hrow = torch.empty(V, P + 1, dtype=torch.int32, device=dev)
+            aflags = torch.empty(V, max(P, 1), dtype=torch.int32, device=dev)
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            work = _lib.u8(lib.gslm_active_union_bytes(P), dev)
+            check(lib.gslm_active_union(self._view_ws(0, V), V, P, work.data_ptr(), work.numel(), ids.data_ptr(),
+                                        hrow.data_ptr(), aflags.data_ptr(), count.data_ptr(), self.stream),
+                  "gslm_active_union")
+            n = int(count.item())
+            self._union = (key, ids[:n], n, hrow, aflags)
+        return self._union[1:]
 
     def active_view(self):
-        return None  # (a union list over several views is not built: cgls_fused takes its ordinary loop)
+        """With union_active=True: this problem restricted to the Gaussians at least one of its views can move
+        (union_list; LMProblem.active_view's argument holds for the union, and the SH-rest coordinates are per
+        Gaussian): a shallow copy whose layout is ParamLayout(Pa, ..., rest_views) and whose products run
+        gslm_tangent_views_active / gslm_gather_views_active on the shared geometries.  None by default, without a
+        current row map in every view, with nothing visible, and with GSLM_CG_ACTIVE=0."""
+        if not self.union_active or self._active is not None or os.environ.get("GSLM_CG_ACTIVE", "1") == "0":
+            return None
+        if any(not vr.tail_clean or vr.N is None for vr in self.views):
+            self._union = None
+            return None
+        ids, na, hrow, aflags = self.union_list()
+        if na == 0:
+            return None  # (every vector of the solve is the exposure tail alone: nothing to save)
+        act = copy.copy(self)
+        act._active = (ids, na)
+        act._union_bufs = (hrow, aflags)
+        act._full = self
+        act.layout = ParamLayout(na, self.layout.K, self.layout.n_exposure, rest_views=self.rest_views)
+        act._bounds, act._damps = act.layout.group_damp_arrays(self.damp)
+        return act
 
     def _mark(self, k):
         if self._events is not None:
@@ -777,10 +821,19 @@ class BatchedLMProblem(LMProblem):
         self._rest_ok = False
         return loss
 
+    def _view_ws(self, c0, c1):
+        ws = (_lib.GslmViewWs * (c1 - c0))()
+        for k, vr in enumerate(self.views[c0:c1]):
+            ws[k].geom, ws[k].scratch = vr.geom.data_ptr(), vr.scratch.data_ptr()
+            ws[k].scratch_bytes, ws[k].num_rendered = vr.scratch.numel(), vr.N
+        return ws
+
     def rest_basis(self):
         """gslm_rest_basis of the batch's views on the current geometry (None in the full layout)."""
         if not self.rest_views:
             return None
+        if self._active is not None:
+            return self._full.rest_basis()  # (the factors are the scene's [P]: the list's kernels read them by id)
         if not self._rest_ok:
             g = raw_gaussians(self.model)
             check(lib.gslm_rest_basis(self._views_arr, self.rest_views, ctypes.byref(g), self._rest_R.data_ptr(),
@@ -833,10 +886,16 @@ class BatchedLMProblem(LMProblem):
                 opts.dot_vy = dot_out
                 opts.dot_scratch = self.dot_scratch.data_ptr()
                 opts.dot_scratch_bytes = self.dot_scratch.numel() * 8
-            ws = (_lib.GslmViewWs * (c1 - c0))()
-            for k, vr in enumerate(self.views[c0:c1]):
-                ws[k].geom, ws[k].scratch = vr.geom.data_ptr(), vr.scratch.data_ptr()
-                ws[k].scratch_bytes, ws[k].num_rendered = vr.scratch.numel(), vr.N
+            ws = self._view_ws(c0, c1)
+            if self._active is not None:  # v and y hold the union list's Gaussians only
+                (ids, na), (hrow, aflags) = self._active, self._union_bufs
+                P = self._full.full_layout.P
+                check(lib.gslm_gather_views_active(self._view_ptr(c0), ws, c1 - c0, ctypes.byref(g), ctypes.byref(vs),
+                                                   ctypes.byref(ys), ids.data_ptr(), na,
+                                                   hrow.data_ptr() + 4 * c0 * (P + 1), P + 1,
+                                                   aflags.data_ptr() + 4 * c0 * P, P, ctypes.byref(opts), self.stream),
+                      "gslm_gather_views_active")
+                continue
             check(lib.gslm_gather_views(self._view_ptr(c0), ws, c1 - c0, ctypes.byref(g), ctypes.byref(vs),
                                         ctypes.byref(ys), ctypes.byref(opts), self.stream), "gslm_gather_views")
 
@@ -887,6 +946,14 @@ class BatchedLMProblem(LMProblem):
                     keep.append(self._pre_opts(opts, v, pre))
                 if R is not None:
                     opts.rest_basis, opts.rest_views, opts.view_base = R.data_ptr(), self.rest_views, c0
+            if self._active is not None:  # v (and s, x of pre) hold the union list's Gaussians only
+                (ids, na), aflags = self._active, self._union_bufs[1]
+                check(lib.gslm_tangent_views_active(self._view_ptr(c0), c1 - c0, ctypes.byref(g), ctypes.byref(vs), 1,
+                                                    ids.data_ptr(), na, aflags.data_ptr() + 4 * c0 * P, P,
+                                                    self._trec.data_ptr() + 32 * c0 * P, P,
+                                                    None if opts is None else ctypes.byref(opts), self.stream),
+                      "gslm_tangent_views_active")
+                continue
             check(lib.gslm_tangent_views(self._view_ptr(c0), c1 - c0, ctypes.byref(g), ctypes.byref(vs), 1,
                                          self._flags.data_ptr() + 4 * c0 * P, P,
                                          self._trec.data_ptr() + 32 * c0 * P, P,
@@ -968,6 +1035,8 @@ def _active_view_for(prob, g, callback):
 def _lean_applies(act, check_every, max_iter):
     """Whether cgls_fused's solve on the active view `act` takes the lean loop (_cgls_lean): benchmark mode (no
     stopping tests), the plain residual, scalars that stay on this device.  GSLM_CG_LEAN=0 keeps the loop below (the switch exists for A/B runs)."""
+    if isinstance(act, BatchedLMProblem):
+        return False  # (the lean loop is the single view's: act.views[0], its parameter block)
     return (not check_every and max_iter >= 1 and not act.ssim and getattr(act, "allreduce_scalars", None) is None
             and os.environ.get("GSLM_CG_LEAN", "1") != "0")
 
@@ -1718,7 +1787,7 @@ def clear_val_cache():
 def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, mask_xyz=True, check_every=True,
             verbose=False, device="cuda", sh_projection="auto", recursion="fused", exchange="auto", group=None,
             val_batch=8, timing=False, backend=None, line_search="union", val_at_start=False, cache_val=True,
-            multiview="loop"):
+            multiview="loop", union_active=False):
     """One LM step of train_jvp.py:237-289: loss, CGLS on the normal equations, backtracking line search.
 
     Single process: LMProblem over `cams` (with one training view the SH-rest group of the CG vectors is carried
@@ -1743,6 +1812,8 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     tangent pass and one gather over the Gaussians for all the views, the SH-rest group in the views' coordinates;
     single process, recursion="fused", mask_xyz=True -- anything else raises ValueError; with one training view the
     existing path runs).  The step comes back in the reference's layout either way.
+    union_active: multiview="batched" only (else ValueError): the batched solve runs on the Gaussians at least one
+    training view can move (BatchedLMProblem(union_active=True)); off by default.
     backend: (problem_cls, evaluator_cls, solver) replacing (LMProblem, LossEvaluator, cgls_fused) -- the CPU
     multi-process tests run this same driver, sharding and reductions on the oracle restatement."""
     import time
@@ -1758,6 +1829,8 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
                              "mask_xyz=True")
         if len(cams) > 1:
             problem_cls = BatchedLMProblem
+    elif union_active:
+        raise ValueError("union_active=True is an option of multiview='batched'")
     t = {}
     clock = [time.perf_counter()]
 
@@ -1776,7 +1849,9 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
         prob = ShardedLMProblem(model, mine, bg, group=group, all_cams=cams, exchange=exchange, mask_xyz=mask_xyz,
                                 damp=damp, device=device, problem_cls=problem_cls)
     else:
-        prob = problem_cls(model, cams, bg, mask_xyz=mask_xyz, damp=damp, device=device, sh_projection=sh_projection)
+        kw = {"union_active": True} if (union_active and problem_cls is BatchedLMProblem) else {}
+        prob = problem_cls(model, cams, bg, mask_xyz=mask_xyz, damp=damp, device=device, sh_projection=sh_projection,
+                           **kw)
     start_loss = prob.evaluate()
     if recursion == "cgls":
         lap("evaluate_rhs_ms")

@@ -488,6 +488,60 @@ int gslm_tangent_views(const gslm_view* views, int32_t nviews, const gslm_gaussi
                        int32_t mask_xyz, const uint32_t* vflags, int64_t flags_stride, float* trec_out,
                        int64_t trec_stride, const gslm_matvec_opts* opts, void* stream);
 
+/* ---- The multi-view product on the Gaussians the batch can move (additive entry points, still ABI 9: no existing
+ * struct or signature changes; gslm.lm.BatchedLMProblem(union_active=True)) ----
+ * The argument of gslm_active_list holds for the union U of the views' lists: off U every view's column of J is
+ * exactly zero, so sum_b J_b^T W_b J_b + D acts there as D alone, J^T b is zero there, and a CG solve from x0 = 0
+ * keeps s, p, q and x exactly zero off U.  The SH-rest coordinates of gslm_rest_basis are per Gaussian, so the
+ * restriction composes with them unchanged.  The two per-Gaussian passes then run on vectors that hold U only.
+ *
+ * gslm_active_union replaces nviews calls of gslm_active_list and the union of their outputs.  ws[b] as for
+ * gslm_gather_views: the geometry and scratch of a view for which GSLM_MV_TAIL_CLEAN may be passed; nviews >= 1
+ * (the list is over the whole batch, not per 16 views).  Outputs, all device memory:
+ *   ids_dev [P]             ids_dev[0 .. *count_dev) = the ascending ids that own a head row in at least one view
+ *                           with num_rendered > 0;
+ *   hrow_dev [nviews][P+1]  hrow[b (P+1) + j] = view b's first head row of list entry j, hrow[b (P+1) + *count_dev]
+ *                           = view b's number of head rows: entry j's head rows in view b are [hrow[b][j],
+ *                           hrow[b][j+1]), an empty range when view b does not move it (the Gaussians between two
+ *                           listed ones own no row in any view);
+ *   aflags_dev [nviews][P]  aflags[b P + j] = gslm_view_flags' word of Gaussian ids[j] in view b;
+ *   count_dev               the list's length, to be read back after the call (stream ordered, no synchronisation).
+ * A view with num_rendered == 0 gets zeros in hrow and aflags and its workspaces are not read.  work is a device
+ * workspace of gslm_active_union_bytes(P) bytes.  GSLM_ERR_INVALID: NULL arguments, nviews < 1, P out of range, a
+ * negative num_rendered or a NULL workspace of a view that rendered; GSLM_ERR_CAPACITY: a scratch below
+ * gslm_scratch_bytes(P, num_rendered) or a work area below gslm_active_union_bytes(P).  Nothing is launched on an
+ * error. */
+size_t gslm_active_union_bytes(int64_t P);
+int gslm_active_union(const gslm_view_ws* ws, int32_t nviews, int64_t P, void* work, size_t work_bytes,
+                      int32_t* ids_dev, uint32_t* hrow_dev, uint32_t* aflags_dev, int64_t* count_dev, void* stream);
+/* gslm_tangent_views on the union list (mask_xyz only): every group of v and of the fused direction update
+ * (xpby_s, x at xpby_x_offset) is [n_active x width] -- row j belongs to Gaussian active_ids[j] -- while g stays the
+ * scene's.  aflags: rows b of gslm_active_union's aflags for the nviews views of this call (flags_stride >=
+ * n_active; P as gslm_active_union wrote them).  The record of list entry j in view b goes to row active_ids[j] of
+ * view b's table (trec_stride >= P), so the RENDER stages that read it (opts->trec_in) are unchanged; the records of
+ * Gaussians off the list are not written and never read (the tile pass reads a record only below a quadrant's
+ * bound, which is the head rule).  opts->rest_basis stays the scene's [P] factors, read by id.  Per-Gaussian
+ * arithmetic is gslm_tangent_views'.  GSLM_ERR_INVALID: as gslm_tangent_views, and mask_xyz == 0, n_active outside
+ * 0..P, a NULL list with n_active > 0, flags_stride < n_active.  Nothing is launched on an error. */
+int gslm_tangent_views_active(const gslm_view* views, int32_t nviews, const gslm_gaussians* g, const gslm_grads* v,
+                              int32_t mask_xyz, const int32_t* active_ids, int64_t n_active, const uint32_t* aflags,
+                              int64_t flags_stride, float* trec_out, int64_t trec_stride,
+                              const gslm_matvec_opts* opts, void* stream);
+/* gslm_gather_views on the union list: every group of v and y is [n_active x width]; hrow / aflags: rows b of
+ * gslm_active_union's outputs for the nviews views of this call (hrow_stride >= n_active + 1, flags_stride >=
+ * n_active).  The row ranges come from hrow, visibility and the SH clamp bits from aflags; the views' tiles, goff,
+ * hscan and clamp words are not read.  Per-element arithmetic, the order of each Gaussian's row sum and the order
+ * of the views are gslm_gather_views': with v zero off the list, y here is bitwise the rows active_ids of the full
+ * product's y; dot_vy sums the same products as (n_active + 255) / 256 partials (dot_scratch >=
+ * gslm_dot_scratch_bytes(n_active)).  opts as gslm_gather_views.  A view with num_rendered == 0 contributes
+ * nothing and its workspaces are not read.  GSLM_ERR_INVALID / GSLM_ERR_CAPACITY: as gslm_gather_views, and
+ * GSLM_ERR_INVALID for n_active outside 0..P, a NULL list, or a stride that does not hold it.  Nothing is launched
+ * on an error. */
+int gslm_gather_views_active(const gslm_view* views, const gslm_view_ws* ws, int32_t nviews, const gslm_gaussians* g,
+                             const gslm_grads* v, const gslm_grads* y, const int32_t* active_ids, int64_t n_active,
+                             const uint32_t* hrow, int64_t hrow_stride, const uint32_t* aflags, int64_t flags_stride,
+                             const gslm_matvec_opts* opts, void* stream);
+
 /* ---- SH-rest coordinates of the Gaussian-sharded exchange (ABI 6) ----
  * The SH-rest column of J for view b is B_rest(dir_b) (x) (d rgb), B_rest the view's SH basis over
  * coefficients 1..nc-1.  So with V views every CGLS iterate started from J^T b keeps each Gaussian's SH-rest

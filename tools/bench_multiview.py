@@ -6,7 +6,9 @@ problem -- by default 1M Gaussians, SH 3, 5 x 1080p views -- through
   loop     gslm.lm.LMProblem: the whole fused product once per view;
   gshard   a one-rank gslm.parallel.GaussianShardedOperator over LMProblem: the exchange's pipeline with device
            copies in place of its all-to-alls;
-  batched  gslm.lm.BatchedLMProblem: gslm_tangent_views, V tile passes, gslm_gather_views.
+  batched  gslm.lm.BatchedLMProblem: gslm_tangent_views, V tile passes, gslm_gather_views;
+  batched_active  BatchedLMProblem(union_active=True): the same solve on the Gaussians at least one view can move
+           (DESIGN.md §4.5c); also emits Pa and P, and the one-off costs of the list, the pack and the unpack.
 Every run times the requested modes one after the other in one process (HIP events around a whole solve, the device
 synchronised at its end), after untimed solves of every mode that keep the GPU busy for >= 200 ms each (the clock
 settle of bench.py).  One JSON line per (run, mode) and one per mode's stage times goes to stdout and, with --out, to
@@ -99,6 +101,9 @@ def main():
         elif m == "batched":
             from gslm.lm import BatchedLMProblem
             p = BatchedLMProblem(model, cams, bg, device=dev)
+        elif m == "batched_active":
+            from gslm.lm import BatchedLMProblem
+            p = BatchedLMProblem(model, cams, bg, device=dev, union_active=True)
         else:
             raise SystemExit(f"unknown mode {m!r}")
         base = next(iter(probs.values()))[0] if (args.share_workspaces and probs) else None
@@ -157,10 +162,36 @@ def main():
         emit({"kind": "agreement", "mode": m, "against": modes[0],
               "rel_norm": float((full(m) - ref).norm() / ref.norm())})
 
+    def timed(fn, reps):
+        fn()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(reps):
+            r = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        return r, e0.elapsed_time(e1) / reps
+
     # per-stage times of one product (events between the stages), direction = the right-hand side
     for m in modes:
         p, g = probs[m]
-        if hasattr(p, "stage_times"):
+        if m == "batched_active":
+            # the list's size and what it costs once per geometry (the list) and once per solve (pack, unpack)
+            def build():
+                p._union = None
+                return p.union_list()
+
+            (_, Pa, _, _), t_list = timed(build, 5)
+            act = p.active_view()
+            if act is None:
+                raise SystemExit("batched_active: no active view (GSLM_CG_ACTIVE=0, or nothing visible)")
+            gp, t_pack = timed(lambda: act.pack(g), args.stage_reps)
+            _, t_unpack = timed(lambda: act.unpack(gp), args.stage_reps)
+            emit({"kind": "active", "mode": m, "Pa": int(Pa), "P_total": int(p.full_layout.P),
+                  "ratio": Pa / max(p.full_layout.P, 1), "union_list_ms": t_list, "pack_ms": t_pack,
+                  "unpack_ms": t_unpack})
+            emit({"kind": "stages", "mode": m, "ms": act.stage_times(gp, reps=args.stage_reps)})
+        elif hasattr(p, "stage_times"):
             emit({"kind": "stages", "mode": m, "ms": p.stage_times(g.clone(), reps=args.stage_reps)})
         else:
             y = p.zeros()
