@@ -755,6 +755,26 @@ static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gs
   if (lean && na < 0) { set_error("matvec: GSLM_MV_LEAN is an option of gslm_matvec_view_active"); return GSLM_ERR_INVALID; }
   const bool dot_defer = lean && lean->dot_defer;
   const int32_t stages = (opts && opts->stages) ? opts->stages : GSLM_STAGE_ALL;
+  // GSLM_MV_EXPOSURE: opts is the base of a gslm_matvec_opts_exposure; RENDER runs the product under the camera's
+  // trained exposure and sums the 12 exposure rows (checked before anything is launched)
+  const gslm_exposure_opts* expo = (opts && (opts->flags & GSLM_MV_EXPOSURE))
+                                       ? &reinterpret_cast<const gslm_matvec_opts_exposure*>(opts)->exposure : nullptr;
+  if (expo) {
+    if (lean || !mask_xyz || opts->pixel_seed || opts->jv_out || (stages & GSLM_STAGE_SCREEN) || opts->trec_in ||
+        opts->rest_basis) {
+      set_error("matvec: GSLM_MV_EXPOSURE needs mask_xyz and excludes pixel_seed, jv_out, the SCREEN stage, trec_in, "
+                "rest_basis and GSLM_MV_LEAN");
+      return GSLM_ERR_INVALID;
+    }
+    if (!expo->exposure || !expo->v_rows || !expo->y_rows || !expo->color || !expo->u_image || !expo->scratch) {
+      set_error("matvec: GSLM_MV_EXPOSURE with a NULL member of gslm_exposure_opts");
+      return GSLM_ERR_INVALID;
+    }
+    if (expo->scratch_bytes < gslm_exposure_scratch_bytes(b.v.H, b.v.W)) {
+      set_error("matvec: GSLM_MV_EXPOSURE scratch below gslm_exposure_scratch_bytes");
+      return GSLM_ERR_CAPACITY;
+    }
+  }
   const double* damp7 = opts ? opts->damp7 : nullptr;
   double* dot_out = opts ? opts->dot_vy : nullptr;
   const bool active = na >= 0;
@@ -861,6 +881,19 @@ static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gs
     if ((stages & GSLM_STAGE_RENDER) &&
         (st = launch_render_vjp_lm(b.v, b.gb, b.bb, b.ib, N, seed, b.sb, opts->flags & GSLM_MV_TAIL_CLEAN, s)))
       return st;
+  } else if (expo) {
+    if (stages & GSLM_STAGE_RENDER) {
+      const ExposureK ex{expo->exposure, expo->v_rows, expo->color, expo->u_image};
+      if (N > 0)
+        st = launch_matvec_render_exposure(b.v, t, b.gb, b.bb, b.ib, b.sb, N, pixel_weight, ex,
+                                           (opts->flags & GSLM_MV_TAIL_CLEAN) != 0, s);
+      else  // an empty list: no tile pass, J v = 0, and the exposure columns alone remain
+        st = launch_exposure_u_empty(b.v.H, b.v.W, ex.color, pixel_weight, ex.V, b.v.stop, ex.u, s);
+      if (st) return st;
+      if ((st = launch_exposure_rows(b.v.H, b.v.W, ex.color, ex.u, ex.V, (float)expo->damp, expo->overwrite != 0,
+                                     b.v.stop, (double*)expo->scratch, expo->y_rows, s)))
+        return st;
+    }
   } else if ((stages & GSLM_STAGE_RENDER) && N > 0 &&
       (st = launch_matvec_render(b.v, t, b.gb, b.bb, b.ib, b.sb, N, pixel_weight, mask_xyz != 0,
                                  opts && (opts->flags & GSLM_MV_TAIL_CLEAN), s)))

@@ -638,6 +638,22 @@ int launch_render_jv(const ViewK& v, const GaussK& t, const GeomBufs& gb, const 
 int launch_matvec_render(const ViewK& v, const GaussK& t, const GeomBufs& gb, const BinBufs& bb, const ImgBufs& ib,
                          const ScratchBufs& sb, int64_t N, const float* weight, bool mask_xyz, bool tail_clean,
                          hipStream_t s);
+// The LM product under a trained per-camera exposure (GSLM_MV_EXPOSURE): X, V = the camera's exposure and the
+// direction's exposure rows (12 device floats each, row-major [3][4]), color = the forward's raw render, u = the
+// [3,H,W] image the tile pass leaves for the exposure rows' reduction (residual.hip).
+struct ExposureK {
+  const float* X;
+  const float* V;
+  const float* color;
+  float* u;
+};
+int launch_matvec_render_exposure(const ViewK& v, const GaussK& t, const GeomBufs& gb, const BinBufs& bb,
+                                  const ImgBufs& ib, const ScratchBufs& sb, int64_t N, const float* weight,
+                                  const ExposureK& ex, bool tail_clean, hipStream_t s);
+int launch_exposure_u_empty(int H, int W, const float* color, const float* weight, const float* V, const double* stop,
+                            float* u, hipStream_t s);
+int launch_exposure_rows(int H, int W, const float* color, const float* u, const float* v_rows, float damp,
+                         bool overwrite, const double* stop, double* part, float* y_rows, hipStream_t s);
 int launch_gather_lm(const ViewK& v, const GaussK& g, const GeomBufs& gb, const ScratchBufs& sb, const GradK& y,
                      const GradK& vin, const double* damp7, bool overwrite, bool mask_xyz, double* dot_part,
                      hipStream_t s, bool rest_proj = false, const int32_t* ids = nullptr, int64_t na = -1,

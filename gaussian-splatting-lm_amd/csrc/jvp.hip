@@ -333,6 +333,90 @@ __global__ __launch_bounds__(256, WITH_XY ? 6 : 8) void k_render_matvec(ViewK v,
                                             write_tail != 0);
 }
 
+// k_render_matvec<false> under a trained per-camera exposure (GSLM_MV_EXPOSURE): between the two passes the
+// 3x4 affine map of gaussian_renderer/__init__.py:113-119 and its transpose.  With dR = J v (the tangent pass's
+// colour, background term included), R the forward's raw render, X the camera's exposure and V the direction's
+// exposure rows:
+//   dC_j = ((dR_0 X[0][j] + dR_1 X[1][j]) + dR_2 X[2][j]) + (((R_0 V[0][j] + R_1 V[1][j]) + R_2 V[2][j]) + V[j][3])
+//   u_j  = 2 w_j dC_j                     -> ex.u (the exposure rows sum R_i u_j and u_j in a streaming pass of their
+//                                            own: this kernel is VALU- and occupancy-bound, a 12-sum block reduction
+//                                            does not belong in it)
+//   ub_i = (X[i][0] u_0 + X[i][1] u_1) + X[i][2] u_2      the back-to-front pass's seed
+// X and V are wave-uniform loads.  With X = [I | 0] and V = 0 every product is by 1 or 0: the rows are those of
+// k_render_matvec<false>.
+__global__ __launch_bounds__(256, 8) void k_render_matvec_exposure(
+    ViewK v, const uint2* __restrict__ ranges, const uint32_t* __restrict__ tile_order,
+    const uint32_t* __restrict__ point_list, const float4* __restrict__ rec, const float4* __restrict__ trec,
+    const uint32_t* __restrict__ slots, const uint2* __restrict__ rect, const uint32_t* __restrict__ goff,
+    const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib, const float* __restrict__ weight,
+    float4* __restrict__ contrib, ExposureK ex) {
+  constexpr int B = MATVEC_BATCH;
+  __shared__ uint64_t s_bits[16];
+  // the LDS plan of k_render_matvec<false>
+  constexpr int kAcc = (vjp_acc_floats<false, false, B>() + 3) / 4 + 31 & ~31;
+  constexpr int kVjp = kAcc + B + B + B / 2;
+  constexpr int kJvp = 4 * 256;
+  __shared__ float4 s_lds[kVjp > kJvp ? kVjp : kJvp];
+  float* s_acc = reinterpret_cast<float*>(s_lds);
+  int* s_misc = reinterpret_cast<int*>(s_lds);
+  float4* s_r0 = s_lds + kAcc;
+  if (cg_stopped(v)) return;
+  const int tile = (int)tile_order[blockIdx.x];
+  const int tile_x = tile % v.gx, tile_y = tile / v.gx;
+  const int tid = threadIdx.x;
+  int px, py;
+  tile_pixel(tile_x, tile_y, tid, px, py);
+  const bool inside = px < v.W && py < v.H;
+  const int64_t pid = (int64_t)py * v.W + px;
+  const int64_t HW = (int64_t)v.H * v.W;
+  const uint2 range = ranges[tile];
+  uint32_t last = 0;
+  float Tf = 0.f, w0 = 0.f, w1 = 0.f, w2 = 0.f;
+  if (inside) {
+    last = n_contrib[pid];
+    Tf = final_T[pid];
+    w0 = weight[pid];
+    w1 = weight[HW + pid];
+    w2 = weight[2 * HW + pid];
+  }
+  JvpPix o;
+  const int q = tid >> 6;
+  const int wm = __builtin_amdgcn_readfirstlane(min(wave_max_u(inside ? (int)last : 0), (int)(range.y - range.x)));
+  jvp_wave_packed(o, (float)px, (float)py, inside ? last : 0u, wm, q, point_list + range.x, rec, trec,
+                  s_lds + 256 * q);
+  // the forward's colour: loaded after the tangent pass (three registers it need not carry)
+  float R0 = 0.f, R1 = 0.f, R2 = 0.f;
+  if (inside) {
+    R0 = ex.color[pid];
+    R1 = ex.color[HW + pid];
+    R2 = ex.color[2 * HW + pid];
+  }
+  const float* __restrict__ X = ex.X;
+  const float* __restrict__ V = ex.V;
+  const float dR0 = o.dC[0] + o.dT * v.bg[0];
+  const float dR1 = o.dC[1] + o.dT * v.bg[1];
+  const float dR2 = o.dC[2] + o.dT * v.bg[2];
+  const float dC0 = ((dR0 * X[0] + dR1 * X[4]) + dR2 * X[8]) + (((R0 * V[0] + R1 * V[4]) + R2 * V[8]) + V[3]);
+  const float dC1 = ((dR0 * X[1] + dR1 * X[5]) + dR2 * X[9]) + (((R0 * V[1] + R1 * V[5]) + R2 * V[9]) + V[7]);
+  const float dC2 = ((dR0 * X[2] + dR1 * X[6]) + dR2 * X[10]) + (((R0 * V[2] + R1 * V[6]) + R2 * V[10]) + V[11]);
+  // u = 2 * w (.) dC   -- factor 2: the [r; r] residual aliasing of batch_training_loss.py:17
+  const float u0 = 2.f * w0 * dC0;
+  const float u1 = 2.f * w1 * dC1;
+  const float u2 = 2.f * w2 * dC2;
+  if (inside) {
+    ex.u[pid] = u0;
+    ex.u[HW + pid] = u1;
+    ex.u[2 * HW + pid] = u2;
+  }
+  const float ub0 = (X[0] * u0 + X[1] * u1) + X[2] * u2;
+  const float ub1 = (X[4] * u0 + X[5] * u1) + X[6] * u2;
+  const float ub2 = (X[8] * u0 + X[9] * u1) + X[10] * u2;
+  VjpPix st;
+  vjp_init(st, v, inside, Tf, last, ub0, ub1, ub2, 0.f);
+  vjp_tile<false, false, 2, B>(st, inside, (float)px, (float)py, tile_x, tile_y, range, point_list, rec, slots, rect,
+                               goff, reinterpret_cast<float2*>(s_r0), s_bits, s_acc, s_misc, contrib, false);
+}
+
 // ------------------------------------------------------------------ launchers
 int launch_jvp(const ViewK& v, const GaussK& g, const GaussK& t, const float* m2t, const GeomBufs& gb,
                const BinBufs& bb, const ImgBufs& ib, const ScratchBufs& sb, float* out_color_t, float* out_inv_t,
@@ -381,6 +465,21 @@ int launch_matvec_render(const ViewK& v, const GaussK& t, const GeomBufs& gb, co
     hipLaunchKernelGGL(k_render_matvec<true>, dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges, bb.tile_order, bb.point_list,
                        gb.rec, sb.trec, bb.slots, gb.rect, gb.goff, ib.final_T, ib.n_contrib, weight, sb.contrib,
                        0);  // no tail rows: the row map holds head entries only
+  GSLM_LAUNCH_CHECK();
+  return GSLM_OK;
+}
+
+int launch_matvec_render_exposure(const ViewK& v, const GaussK& t, const GeomBufs& gb, const BinBufs& bb,
+                                  const ImgBufs& ib, const ScratchBufs& sb, int64_t N, const float* weight,
+                                  const ExposureK& ex, bool tail_clean, hipStream_t s) {
+  const int ntiles = v.gx * v.gy;
+  if (!tail_clean) {
+    const int st = launch_lm_rowmap(v, gb, bb, ib, sb, N, s);
+    if (st) return st;
+  }
+  hipLaunchKernelGGL(k_render_matvec_exposure, dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges, bb.tile_order,
+                     bb.point_list, gb.rec, sb.trec, bb.slots, gb.rect, gb.goff, ib.final_T, ib.n_contrib, weight,
+                     sb.contrib, ex);
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
 }

@@ -80,6 +80,21 @@ class GslmMatvecOptsLean(ctypes.Structure):
     _fields_ = [("base", GslmMatvecOpts), ("lean", GslmCgLean)]
 
 
+class GslmExposureOpts(ctypes.Structure):
+    """gslm_exposure_opts: one view's product under its camera's trained exposure."""
+    _fields_ = [
+        ("exposure", ctypes.c_void_p), ("v_rows", ctypes.c_void_p), ("y_rows", ctypes.c_void_p),
+        ("color", ctypes.c_void_p), ("u_image", ctypes.c_void_p), ("scratch", ctypes.c_void_p),
+        ("scratch_bytes", ctypes.c_size_t), ("damp", ctypes.c_double), ("overwrite", ctypes.c_int32),
+        ("_pad", ctypes.c_int32),
+    ]
+
+
+class GslmMatvecOptsExposure(ctypes.Structure):
+    """gslm_matvec_opts_exposure: the product's options with GSLM_MV_EXPOSURE set in base.flags."""
+    _fields_ = [("base", GslmMatvecOpts), ("exposure", GslmExposureOpts)]
+
+
 class GslmViewWs(ctypes.Structure):
     """gslm_view_ws: one view's workspaces for gslm_gather_views."""
     _fields_ = [
@@ -279,6 +294,11 @@ EXPORTS = {
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int32,
                                         ctypes.c_void_p]),
+    "gslm_exposure_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
+    "gslm_lm_residual_exposure": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                 ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
     "gslm_ssim_state_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
     "gslm_ssim_residual": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                           ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_size_t,

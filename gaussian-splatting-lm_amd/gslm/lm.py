@@ -32,6 +32,7 @@ STAGE_OVERWRITE = 8
 MV_TAIL_CLEAN = 1  # gslm_matvec_opts.flags: GSLM_MV_TAIL_CLEAN
 MV_SH_REST_PROJECTED = 2  # GSLM_MV_SH_REST_PROJECTED
 MV_LEAN = 4  # GSLM_MV_LEAN
+MV_EXPOSURE = 8  # GSLM_MV_EXPOSURE
 
 DEFAULT_DAMP = {"xyz": 5e2, "features_dc": 5e-2, "features_rest": 5e-2, "scaling": 5e-2, "rotation": 5e-2,
                 "opacity": 5e-2, "exposure": 1e1}
@@ -164,9 +165,17 @@ class LMProblem:
     """The LM normal equations of one camera batch (one LM step's worth of cached geometry)."""
 
     def __init__(self, model, cams, bg, gts=None, alpha_masks=None, mask_xyz=True, damp=None, device="cuda",
-                 ssim=False, lambda_dssim=0.2, sh_projection=False):
+                 ssim=False, lambda_dssim=0.2, sh_projection=False, train_exposure=False):
         """ssim=False: the residual train_jvp.py uses (disable_ssim=True, [r; r]); ssim=True: the
         [r1; r2] residual with the SSIM term (batch_training_loss.py:18-30, gslm_ssim_*).
+
+        train_exposure: the residual is taken on the exposed colour C = R X[:3, :3] + X[:3, 3] of each camera's row
+        X of model._exposure (render()'s use_trained_exp, gaussian_renderer/__init__.py:113-119), and the exposure
+        rows of the batch's cameras are unknowns of the normal equations: J^T b and (J^T J + D) v carry them in the
+        layout's exposure tail (GSLM_MV_EXPOSURE, gslm_lm_residual_exposure).  Single process, mask_xyz=True,
+        ssim=False; every camera's image_name must be in model.exposure_mapping and the model must not carry
+        pretrained exposures (they are not parameters) -- ValueError otherwise.  Both SH-rest layouts and the active
+        list apply unchanged (the exposure rows ride in the flat tail); the lean CG loop does not.
 
         sh_projection: param-space vectors carry the SH-rest group as 3 coordinates per Gaussian along the
         view's unit basis direction (GSLM_MV_SH_REST_PROJECTED; one view only -- with one view the CG
@@ -180,6 +189,9 @@ class LMProblem:
         self.device = device
         self.bg = bg
         self.mask_xyz = bool(mask_xyz)
+        self.train_exposure = bool(train_exposure)
+        if self.train_exposure:
+            self._init_exposure(model, cams, device)
         P = model._xyz.shape[0]
         K = 1 + model._features_rest.shape[1]
         if sh_projection == "auto":
@@ -207,18 +219,43 @@ class LMProblem:
         self.res_scratch = torch.empty(lib.gslm_residual_scratch_bytes(1, 1) // 8, dtype=torch.float64,
                                        device=device)
 
+    def _init_exposure(self, model, cams, device):
+        if self.ssim or not self.mask_xyz:
+            raise ValueError("train_exposure runs on the LM rows with the plain residual (mask_xyz=True, ssim=False)")
+        if getattr(model, "pretrained_exposures", None) is not None:
+            raise ValueError("train_exposure: the model renders with pretrained exposures, which are not parameters")
+        missing = [c.image_name for c in cams if c.image_name not in model.exposure_mapping]
+        if missing:
+            raise ValueError(f"train_exposure: no row of model._exposure for {missing} (model.exposure_mapping)")
+        X = model._exposure
+        if X.dtype != torch.float32 or not X.is_contiguous() or X.shape[1:] != (3, 4):
+            raise ValueError("train_exposure: model._exposure must be contiguous float32 [n, 3, 4]")
+        self.exp_idx = [int(model.exposure_mapping[c.image_name]) for c in cams]
+        self._exp_rhs = torch.zeros(X.numel(), dtype=torch.float32, device=device)  # the exposure rows of J^T b
+        self._exp_u = [None] * len(cams)
+        self._exp_scratch = torch.empty(lib.gslm_exposure_scratch_bytes(1, 1) // 8, dtype=torch.float64,
+                                        device=device)
+        seen = set()  # the first view of each camera writes that camera's rows of y (and adds D v there)
+        self._exp_first = [not (i in seen or seen.add(i)) for i in self.exp_idx]
+        rest = sorted(set(range(X.shape[0])) - seen)
+        self._exp_rest = torch.tensor(rest, dtype=torch.long, device=device) if rest else None
+
     # -------------------------------------------------------------- residual (A8)
     def evaluate(self):
         """Primal forward of every view; residuals, per-pixel weights and the J^T b seeds from one fused
         epilogue per view (gslm_lm_residual); loss = 2 sum ||r||^2 (device double)."""
         g = raw_gaussians(self.model)
         loss = torch.zeros((), dtype=torch.float64, device=self.device)
+        if self.train_exposure:
+            self._exp_rhs.zero_()
         for b, vr in enumerate(self.views):
             R = vr.forward(g, self.stream, want_invdepth=False)
             if self.residuals[b] is None or self.residuals[b].shape != R.shape:
                 self.residuals[b] = torch.empty_like(R)
                 self.weights[b] = torch.empty_like(R)
                 self.seeds[b] = torch.empty_like(R)
+                if self.train_exposure:
+                    self._exp_u[b] = torch.empty_like(R)
             m = self.masks[b]
             gt = self.gts[b]
             if m is not None:
@@ -239,6 +276,17 @@ class LMProblem:
                                              st.numel(), None, None, self.seeds[b].data_ptr(), loss.data_ptr(),
                                              int(b > 0), self.stream), "gslm_ssim_residual")
                 continue
+            if self.train_exposure:
+                # the same epilogue on the exposed colour; R stays in vr.color for the products.  The seed is dL/dR
+                # (the exposure's transpose applied), so rhs() seeds the back-to-front pass as ever
+                check(lib.gslm_lm_residual_exposure(
+                    vr.H, vr.W, R.data_ptr(), gt.data_ptr(), None if m is None else m.data_ptr(),
+                    self.model._exposure.data_ptr() + 48 * self.exp_idx[b], self.residuals[b].data_ptr(),
+                    self.weights[b].data_ptr(), self.seeds[b].data_ptr(),
+                    self._exp_rhs.data_ptr() + 48 * self.exp_idx[b], self._exp_scratch.data_ptr(),
+                    self._exp_scratch.numel() * 8, loss.data_ptr(), int(b > 0), self.stream),
+                    "gslm_lm_residual_exposure")
+                continue
             check(lib.gslm_lm_residual(vr.H, vr.W, R.data_ptr(), gt.data_ptr(), None if m is None else m.data_ptr(),
                                        self.residuals[b].data_ptr(), self.weights[b].data_ptr(),
                                        self.seeds[b].data_ptr(), self.res_scratch.data_ptr(),
@@ -252,7 +300,8 @@ class LMProblem:
 
     # -------------------------------------------------------------- J^T b
     def rhs(self, out, fused=True):
-        """out = J^T b = -2 sum_b J_b^T (m (.) 1[0<=R<=1] (.) r_b) in the flat layout (xyz, exposure zeroed).
+        """out = J^T b = -2 sum_b J_b^T (m (.) 1[0<=R<=1] (.) r_b) in the flat layout (xyz zeroed; exposure zeroed,
+        or with train_exposure the rows evaluate() summed: G[i][j] = sum R_i sC_j, G[j][3] = sum sC_j).
 
         fused: the LM path -- a back-to-front pass seeded with gslm_lm_residual's seed into the LM
         rows, then the LM gather (gslm_matvec_view_ex with pixel_seed); otherwise the drop-in
@@ -273,7 +322,10 @@ class LMProblem:
             if not self.views:
                 out.zero_()
             e0, e1 = self.layout.offsets["exposure"]
-            out[e0:e1].zero_()
+            if self.train_exposure:
+                out[e0:e1].copy_(self._exp_rhs)
+            else:
+                out[e0:e1].zero_()
             return self._mark_rhs(out)
         if self.layout.rest_projected:
             full = torch.zeros(self.full_layout.numel, dtype=torch.float32, device=self.device)
@@ -290,9 +342,11 @@ class LMProblem:
         return out
 
     def exposure_is_zero(self, g):
-        """Whether the exposure slice of the right-hand side g is zero, so that every CG iterate's is (J has no
-        exposure column): true without a device read for the rhs() this problem produced and nobody modified
-        since; otherwise checked on the device (one host sync per solve)."""
+        """Whether the exposure slice of the right-hand side g is zero, so that every CG iterate's is (without
+        train_exposure J has no exposure column): true without a device read for the rhs() this problem produced and
+        nobody modified since; otherwise checked on the device (one host sync per solve).  Never with train_exposure."""
+        if self.train_exposure:
+            return False
         if self.rhs_is_mine(g):
             return True
         e0, e1 = self.layout.offsets["exposure"]
@@ -314,6 +368,9 @@ class LMProblem:
                                     vr.scratch.numel(), ctypes.byref(grads), self.stream), "gslm_backward")
             vr.tail_clean = False
         self._apply_mask(out, self.full_layout)
+        if self.train_exposure:
+            e0, e1 = self.full_layout.offsets["exposure"]
+            out[e0:e1].copy_(self._exp_rhs)
         return out
 
     # -------------------------------------------------------------- SH-rest projection (sh_projection)
@@ -359,7 +416,8 @@ class LMProblem:
         o = (layout or self.layout).offsets
         if self.mask_xyz:
             vec[o["xyz"][0]:o["xyz"][1]].zero_()
-        vec[o["exposure"][0]:o["exposure"][1]].zero_()
+        if not self.train_exposure:
+            vec[o["exposure"][0]:o["exposure"][1]].zero_()
 
     # -------------------------------------------------------------- (J^T J + D) v
     def matvec(self, v, y, cg_ctl=None):
@@ -380,8 +438,10 @@ class LMProblem:
         zero already -- true of every CG iterate (J has no exposure column, x0 = 0, y is the solver's own
         q) -- so y's exposure slice D v = 0 is left as it is (no elementwise launch per product).
         cg_ctl: device pointer of cgls_fused's CG control block (gslm_cg_monitor): once its stopping tests
-        have fired the product's kernels return at once (gslm_matvec_opts.cg_ctl)."""
-        fuse = dot_out is not None and len(self.views) == 1
+        have fired the product's kernels return at once (gslm_matvec_opts.cg_ctl).
+        With train_exposure nothing is fused (False): the gather's dot covers the Gaussian groups only, and
+        <v, y> must include the exposure tail -- the caller takes its own dot over the whole vector."""
+        fuse = dot_out is not None and len(self.views) == 1 and not self.train_exposure
         self.local_normal_matvec(v, y, damp=True, dot_out=dot_out if fuse else None, pre=pre,
                                  exposure_zero=exposure_zero, cg_ctl=cg_ctl)
         return fuse
@@ -422,15 +482,42 @@ class LMProblem:
             if self.ssim:
                 self._ssim_product(b, vr, g, vs, ys, opts)
                 continue
+            if self.train_exposure:
+                if lean is not None:
+                    raise ValueError("the lean CG loop was written for a zero exposure tail")
+                opts = self._exposure_opts(opts, b, vr, v, y, e0, damp)
             self._view_product(vr, g, vs, self.weights[b].data_ptr(), ys, opts, "gslm_matvec_view_ex", lean=lean)
             vr.tail_clean = True
-        if exposure_zero:
+        if self.train_exposure:
+            # the batch's cameras' rows are written by their views (above); the other cameras' are D v alone
+            if self._exp_rest is not None:
+                vt, yt = v[e0:e1].view(-1, 12), y[e0:e1].view(-1, 12)
+                yt[self._exp_rest] = vt[self._exp_rest] * (float(self._damps[6]) if damp else 0.0)
+        elif exposure_zero:
             pass  # y[e0:e1] = D v[e0:e1] = 0 already (matvec_dot)
         elif damp:
             torch.mul(v[e0:e1], float(self._damps[6]), out=y[e0:e1])  # J has no exposure column
         else:
             y[e0:e1].zero_()
         return y
+
+    def _exposure_opts(self, opts, b, vr, v, y, e0, damp):
+        """View b's options extended by its camera's exposure (GSLM_MV_EXPOSURE): X from the model, V and Y the
+        camera's 12 floats of v's and y's exposure tail; the camera's first view writes Y and adds D V."""
+        ext = _lib.GslmMatvecOptsExposure()
+        ctypes.memmove(ctypes.addressof(ext.base), ctypes.addressof(opts), ctypes.sizeof(opts))
+        ext.base.flags |= MV_EXPOSURE
+        k = self.exp_idx[b]
+        x = ext.exposure
+        x.exposure = self.model._exposure.data_ptr() + 48 * k
+        x.v_rows = v.data_ptr() + 4 * (e0 + 12 * k)
+        x.y_rows = y.data_ptr() + 4 * (e0 + 12 * k)
+        x.color = vr.color.data_ptr()
+        x.u_image = self._exp_u[b].data_ptr()
+        x.scratch, x.scratch_bytes = self._exp_scratch.data_ptr(), self._exp_scratch.numel() * 8
+        x.overwrite = int(self._exp_first[b])
+        x.damp = float(self._damps[6]) if (damp and self._exp_first[b]) else 0.0
+        return ext
 
     def _view_product(self, vr, g, vs, weight, ys, opts, what, lean=None):
         """gslm_matvec_view_ex on one view -- or, on an active_view() (v and y hold the listed Gaussians only),
@@ -520,6 +607,8 @@ class LMProblem:
     def screen_products(self, v, screen, pre=None, cg_ctl=None):
         """screen[b] = this rank's view b's per-Gaussian screen-space sums S_b^T W_b J_b v (P x 8,
         GSLM_STAGE_SCREEN); pre as in matvec_dot (applied with the first view)."""
+        if self.train_exposure:
+            raise ValueError("the sharded exchanges do not carry trained exposure")
         g = raw_gaussians(self.model)
         vs = self.layout.grads_struct(v)
         ys = self.layout.grads_struct(v)  # unused by the SCREEN stage
@@ -580,8 +669,8 @@ class LMProblem:
     def jv_residual(self, v, rmasks, out):
         """out[b] = J_r,b v = m 1[0 <= R <= 1] (.) (d R_b / d theta) v  (the `matvec` of solver_functions.py:83-93,
         one copy of the [r; r] pair)."""
-        if self.ssim:
-            raise ValueError("jv_residual: the disable_ssim residual only")
+        if self.ssim or self.train_exposure:
+            raise ValueError("jv_residual: the disable_ssim residual without trained exposure only")
         g = raw_gaussians(self.model)
         vs = self.layout.grads_struct(v)
         for b, vr in enumerate(self.views):
@@ -599,6 +688,8 @@ class LMProblem:
     def jt_residual(self, r, rmasks, out):
         """out = J^T [r; r] = 2 sum_b J_r,b^T r_b (the `matvec_T` of solver_functions.py:101-132), xyz and exposure
         groups zero.  Overwrites out."""
+        if self.train_exposure:
+            raise ValueError("jt_residual: the residual-space recursion does not carry trained exposure")
         g = raw_gaussians(self.model)
         ys = self.layout.grads_struct(out)
         for b, vr in enumerate(self.views):
@@ -1037,6 +1128,8 @@ def _lean_applies(act, check_every, max_iter):
     stopping tests), the plain residual, scalars that stay on this device.  GSLM_CG_LEAN=0 keeps the loop below (the switch exists for A/B runs)."""
     if isinstance(act, BatchedLMProblem):
         return False  # (the lean loop is the single view's: act.views[0], its parameter block)
+    if getattr(act, "train_exposure", False):
+        return False  # (the lean kernels were written for a zero exposure tail)
     return (not check_every and max_iter >= 1 and not act.ssim and getattr(act, "allreduce_scalars", None) is None
             and os.environ.get("GSLM_CG_LEAN", "1") != "0")
 
@@ -1295,6 +1388,8 @@ def cgls_residual(prob, max_iter=10, restart_iter=10, tol=1e-10, atol=0.0, verbo
     rounding path.  b = -[r; r] (train_jvp.py:243), x0 = 0.  Returns (x, info)."""
     if getattr(prob, "ssim", False):
         raise ValueError("cgls_residual: the disable_ssim residual only")
+    if getattr(prob, "train_exposure", False):
+        raise ValueError("cgls_residual: the residual-space recursion does not carry trained exposure")
     dev = prob.device
     rm = prob.residual_masks()
     b = [-r for r in prob.residuals]  # b = -[r; r]: one copy per view
@@ -1406,8 +1501,23 @@ class LossEvaluator:
     same).  `reduce`: a callable summing it over the ranks that hold the other views (gslm.parallel.allreduce_loss)."""
 
     def __init__(self, model, cams, bg, device="cuda", batch=8, gts=None, alpha_masks=None, reduce=None, streams=3,
-                 device_count=False):
+                 device_count=False, train_exposure=False):
+        """train_exposure: the loss is taken on the exposed colour of each camera's row of model._exposure, as
+        LMProblem(train_exposure=True) takes it: 2 sum ||m clamp01(C) - gt||^2.  evaluate() then renders each view
+        with the full forward and runs gslm_lm_residual_exposure in its loss-only mode (no fused loss epilogue, no
+        side streams); evaluate_points -- the union line search -- renders no exposure and raises ValueError."""
         self.model = model
+        self.train_exposure = bool(train_exposure)
+        if self.train_exposure:
+            if getattr(model, "pretrained_exposures", None) is not None:
+                raise ValueError("train_exposure: the model renders with pretrained exposures, which are not parameters")
+            missing = [c.image_name for c in cams if c.image_name not in model.exposure_mapping]
+            if missing:
+                raise ValueError(f"train_exposure: no row of model._exposure for {missing} (model.exposure_mapping)")
+            self.exp_idx = [int(model.exposure_mapping[c.image_name]) for c in cams]
+            self._exp_scratch = torch.empty(lib.gslm_exposure_scratch_bytes(1, 1) // 8, dtype=torch.float64,
+                                            device=device)
+            self._exp_raster = {}  # (H, W) -> the ViewRaster whose workspaces the views of that size share
         # True: evaluations after the first render through gslm_rasterize_loss_dev (no count read-back per batch).
         # Measured at 50 1080p views, 8 streams: 0.347 ms per view against 0.339 with the per-batch read-back
         # (profiles/r03/val_loss_devcount.json) -- the read-back costs less than the capacity-sized tile sort
@@ -1482,6 +1592,8 @@ class LossEvaluator:
 
     def evaluate(self):
         """Device double: the loss over this evaluator's views (summed over the ranks with `reduce`)."""
+        if self.train_exposure:
+            return self._evaluate_exposure()
         g = raw_gaussians(self.model)
         P = g.P
         V = len(self.views)
@@ -1574,6 +1686,33 @@ class LossEvaluator:
             self.reduce(loss)
         return loss
 
+    def _evaluate_exposure(self):
+        """evaluate() with train_exposure: per view the forward, then the exposure residual's loss alone."""
+        g = raw_gaussians(self.model)
+        V = len(self.views)
+        losses = torch.zeros(max(V, 1), dtype=torch.float64, device=self.device)
+        X = self.model._exposure
+        if X.dtype != torch.float32 or not X.is_contiguous():
+            raise ValueError("train_exposure: model._exposure must be contiguous float32 [n, 3, 4]")
+        stream = _lib.stream_handle(self.device)
+        for i, vw in enumerate(self.views):
+            key = (vw.image_height, vw.image_width)
+            vr = self._exp_raster.get(key)
+            if vr is None:
+                vr = self._exp_raster[key] = ViewRaster(vw, self.device)
+            vr.view = vw
+            R = vr.forward(g, stream, want_invdepth=False)
+            self.num_rendered[i] = vr.N
+            m = self.masks[i]
+            check(lib.gslm_lm_residual_exposure(
+                vr.H, vr.W, R.data_ptr(), self.gts[i].data_ptr(), None if m is None else m.data_ptr(),
+                X.data_ptr() + 48 * self.exp_idx[i], None, None, None, None, self._exp_scratch.data_ptr(),
+                self._exp_scratch.numel() * 8, losses.data_ptr() + 8 * i, 0, stream), "gslm_lm_residual_exposure")
+        loss = losses[:V].sum() if V else losses[0]
+        if self.reduce is not None:
+            self.reduce(loss)
+        return loss
+
     # ---- the line search's six points with one binning per view (include/gslm.h "shared binning", ABI 8) ----
     def _sets_scratch(self, k, n, H, W):
         """Batch position k's per-tile partials of the all-sets blend (its stream's own buffer)."""
@@ -1629,6 +1768,8 @@ class LossEvaluator:
         Pipelining: a batch's preprocesses, union geometries and pair-count read-back run on the main stream while the
         previous batch's binnings and blends run on the side streams (two alternating slot sets), so the read-back does
         not drain the device.  union_counts[i]: view i's union list length (the last call)."""
+        if self.train_exposure:
+            raise ValueError("evaluate_points renders no exposure: with train_exposure the line search is exact")
         n = len(sets)
         if not 1 <= n <= 8:
             raise ValueError("evaluate_points takes 1..8 parameter sets")
@@ -1750,7 +1891,8 @@ _LS_GROUPS = ("_features_dc", "_features_rest", "_scaling", "_rotation", "_opaci
 
 def param_snapshot(model):
     """A line-search point's parameters for LossEvaluator.evaluate_points: clones of the groups the LM step moves,
-    the model's own (frozen) xyz tensor.  The exposure group is not rendered by the validation loss."""
+    the model's own (frozen) xyz tensor.  The exposure group is not part of a snapshot: evaluate_points renders no
+    exposure, so lm_step(train_exposure=True) searches in the exact order instead."""
     import types
     ns = types.SimpleNamespace(_xyz=model._xyz, active_sh_degree=model.active_sh_degree)
     with torch.no_grad():
@@ -1787,7 +1929,7 @@ def clear_val_cache():
 def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, mask_xyz=True, check_every=True,
             verbose=False, device="cuda", sh_projection="auto", recursion="fused", exchange="auto", group=None,
             val_batch=8, timing=False, backend=None, line_search="union", val_at_start=False, cache_val=True,
-            multiview="loop", union_active=False):
+            multiview="loop", union_active=False, train_exposure=False):
     """One LM step of train_jvp.py:237-289: loss, CGLS on the normal equations, backtracking line search.
 
     Single process: LMProblem over `cams` (with one training view the SH-rest group of the CG vectors is carried
@@ -1814,6 +1956,11 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     existing path runs).  The step comes back in the reference's layout either way.
     union_active: multiview="batched" only (else ValueError): the batched solve runs on the Gaussians at least one
     training view can move (BatchedLMProblem(union_active=True)); off by default.
+    train_exposure: the step also moves the exposure rows of the training cameras (LMProblem(train_exposure=True)),
+    and the validation loss is taken under each validation camera's exposure (LossEvaluator(train_exposure=True)).
+    The line search then runs in the exact order (the union evaluator renders no exposure).  Single process,
+    multiview="loop", recursion="fused", mask_xyz=True -- anything else raises ValueError.  Off by default: nothing
+    changes, and model._exposure is not touched.
     backend: (problem_cls, evaluator_cls, solver) replacing (LMProblem, LossEvaluator, cgls_fused) -- the CPU
     multi-process tests run this same driver, sharding and reductions on the oracle restatement."""
     import time
@@ -1831,6 +1978,10 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
             problem_cls = BatchedLMProblem
     elif union_active:
         raise ValueError("union_active=True is an option of multiview='batched'")
+    if train_exposure and (sharded or multiview != "loop" or recursion != "fused" or not mask_xyz):
+        raise ValueError("train_exposure=True is the single-process step with multiview='loop', recursion='fused' "
+                         "and mask_xyz=True")
+    exp_kw = {"train_exposure": True} if train_exposure else {}
     t = {}
     clock = [time.perf_counter()]
 
@@ -1851,7 +2002,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     else:
         kw = {"union_active": True} if (union_active and problem_cls is BatchedLMProblem) else {}
         prob = problem_cls(model, cams, bg, mask_xyz=mask_xyz, damp=damp, device=device, sh_projection=sh_projection,
-                           **kw)
+                           **kw, **exp_kw)
     start_loss = prob.evaluate()
     if recursion == "cgls":
         lap("evaluate_rhs_ms")
@@ -1879,7 +2030,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     # next while the model, the validation cameras (held by it, so their ids stay theirs) and the settings are the same
     imgs = [(getattr(c, "original_image", None), getattr(c, "alpha_mask", None)) for c in mine_val]
     vkey = (id(model), model.active_sh_degree, tuple(id(c) for c in mine_val), tuple(id(t) for p in imgs for t in p),
-            str(device), val_batch, evaluator_cls, sharded, id(group),
+            str(device), val_batch, evaluator_cls, sharded, id(group), bool(train_exposure),
             tuple(float(x) for x in torch.as_tensor(bg).reshape(-1).tolist()))
     hit = _VAL_CACHE.get("last") if cache_val else None
     if hit is not None and hit[0] == vkey:
@@ -1889,7 +2040,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     else:
         _VAL_CACHE.pop("last", None)
         val = evaluator_cls(model, mine_val, bg, device=device, batch=val_batch,
-                            reduce=(lambda x: allreduce_loss(x, group)) if sharded else None,
+                            reduce=(lambda x: allreduce_loss(x, group)) if sharded else None, **exp_kw,
                             # (GSLM_VAL_STREAMS: the side-stream count, an A/B override of LossEvaluator's default)
                             **({"streams": int(os.environ["GSLM_VAL_STREAMS"])} if "GSLM_VAL_STREAMS" in os.environ else {}))
         if cache_val:
@@ -1900,7 +2051,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
         lap("val_start_ms")
     if line_search not in ("union", "exact"):
         raise ValueError(f"line_search must be 'union' or 'exact', got {line_search!r}")
-    union = line_search == "union" and mask_xyz and hasattr(val, "evaluate_points")
+    union = line_search == "union" and mask_xyz and hasattr(val, "evaluate_points") and not train_exposure
     # train_jvp.py:262-279: alpha = 2, 1, ..., 1/16 on the validation views, keep the best, step to it
     alpha = 2.0
     best_alpha, best_loss = alpha, math.inf

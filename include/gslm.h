@@ -235,7 +235,8 @@ int gslm_jvp(const gslm_view* view, const gslm_gaussians* g, const gslm_gaussian
 /* ---- fused LM normal-equations product of one view:
  *   y += 2 * J^T ( w (.) (J v) )     (J: d clamp-free render / d raw params, g->raw must be 1)
  * w [3,H,W] is the per-pixel weight m^2 * 1[0 <= R <= 1] of the disable_ssim residual
- * (batch_training_loss.py:10-17; the factor 2 is the [r; r] aliasing).
+ * (batch_training_loss.py:10-17; the factor 2 is the [r; r] aliasing).  This J has no exposure
+ * column; GSLM_MV_EXPOSURE (below) is the product with the cameras' trained exposures.
  * mask_xyz = 1 freezes the xyz group (train_jvp.py:221-227): v.xyz is ignored, y.xyz untouched. ---- */
 int gslm_matvec_view(const gslm_view* view, const gslm_gaussians* g, const gslm_grads* v,
                      const float* pixel_weight, int32_t mask_xyz, const void* geom, const void* binning,
@@ -271,7 +272,8 @@ typedef struct gslm_matvec_opts {
   int32_t stages;         /* GSLM_STAGE_* bits; 0 means GSLM_STAGE_ALL (accumulate) */
   int32_t flags;          /* GSLM_MV_* bits */
   const double* damp7;    /* host array (GaussianModelDampMatrix order: xyz, dc, rest, scaling, rotation,
-                             opacity, exposure) or NULL; when set GATHER also adds D v (exposure untouched) */
+                             opacity, exposure) or NULL; when set GATHER also adds D v (exposure untouched: the
+                             tail is the caller's, or gslm_exposure_opts.damp's with GSLM_MV_EXPOSURE) */
   double* dot_vy;         /* device double or NULL: receives <v, y> over the gathered groups after GATHER */
   void* dot_scratch;      /* device scratch for dot_vy, >= gslm_dot_scratch_bytes(P) bytes */
   size_t dot_scratch_bytes;
@@ -422,6 +424,57 @@ int gslm_cg_end_active(const float* x, const float* p, const double* num_dev, co
                        const int32_t* pos_dev, int64_t n_active, int64_t P, const int32_t* widths, int32_t ngroups,
                        int64_t tail_n, float* out_full, const void* fin_partials, int32_t fin_np, double* fin_dev,
                        void* stream);
+
+/* ---- The single-view product under a trained per-camera exposure (additive entry points, still ABI 9; DESIGN.md
+ * 4.5d; gslm.lm.LMProblem(train_exposure=True)) ----
+ * render() maps the raw render R through the camera's 3x4 exposure X before the clamp
+ * (gaussian_renderer/__init__.py:113-119): C_j = sum_i R_i X[i][j] + X[j][3].  With it the residual is
+ * r_j = m clamp(C_j, 0, 1) - gt_j, and J gains the 12 columns dC/dX of every camera of the batch.  For a direction
+ * (v, V), V the 3x4 exposure rows of v (row-major [i][k], as X):
+ *   dC_j = sum_i (J v)_i X[i][j] + sum_i R_i V[i][j] + V[j][3],      u_j = 2 w_j dC_j,  w = m^2 1[0 <= C <= 1]
+ *   Gaussian rows  y += J^T ub,  ub_i = sum_j X[i][j] u_j
+ *   exposure rows  Y[i][j] += sum_pix R_i u_j  (j < 3),   Y[j][3] += sum_pix u_j.
+ * GSLM_MV_EXPOSURE in opts->flags: opts points to the base member of a gslm_matvec_opts_exposure and the RENDER stage
+ * runs this product: the tile pass forms dC, u and ub between its two halves and leaves u in u_image; a streaming
+ * pass sums the 12 exposure rows (double block partials, one final pass in fixed order: deterministic) into
+ *   y_rows[k] = [y_rows[k] unless overwrite] + damp v_rows[k] + sum_k.
+ * pixel_weight is gslm_lm_residual_exposure's weight.  Accepted by gslm_matvec_view_ex and gslm_matvec_view_active
+ * (the exposure rows are part of the flat tail, which gslm_active_pack copies).  dot_vy covers the Gaussian groups
+ * only: the caller adds the tail's <V, Y>.  GSLM_ERR_INVALID (nothing launched): with pixel_seed, jv_out,
+ * GSLM_STAGE_SCREEN, trec_in, rest_basis, GSLM_MV_LEAN or mask_xyz = 0, or a NULL member; GSLM_ERR_CAPACITY: scratch
+ * below gslm_exposure_scratch_bytes.  With cg_ctl[0] != 0 neither y nor y_rows nor u_image is written. */
+#define GSLM_MV_EXPOSURE 8
+typedef struct gslm_exposure_opts {
+  const float* exposure;  /* X: 12 device floats, the camera's row of GaussianModel._exposure */
+  const float* v_rows;    /* V: 12 device floats, the camera's exposure rows of v (read after the TANGENT stage's
+                             fused direction update, which covers the tail) */
+  float* y_rows;          /* Y: 12 device floats, the camera's exposure rows of y */
+  const float* color;     /* [3,H,W]: the forward's out_color (the raw render R) */
+  float* u_image;         /* [3,H,W] scratch: receives u */
+  void* scratch;          /* >= gslm_exposure_scratch_bytes(H, W) */
+  size_t scratch_bytes;
+  double damp;            /* y_rows += damp v_rows (pass it with one view per camera and product) */
+  int32_t overwrite;      /* nonzero: y_rows is written, not accumulated into */
+  int32_t _pad;
+} gslm_exposure_opts;
+typedef struct gslm_matvec_opts_exposure {
+  gslm_matvec_opts base;
+  gslm_exposure_opts exposure;
+} gslm_matvec_opts_exposure;
+size_t gslm_exposure_scratch_bytes(int32_t H, int32_t W);
+/* gslm_lm_residual on the exposed colour C (above), exposure = X (12 device floats):
+ *   residual = m clamp(C, 0, 1) - gt,   weight = m^2 1[0 <= C <= 1]                     (NULL: not written)
+ *   seed_i   = sum_j X[i][j] sC_j,  sC_j = -2 m 1[0 <= C_j <= 1] residual_j              (NULL: not written)
+ *              -- dL/dR of J^T b: feed it to pixel_seed as gslm_lm_residual's
+ *   rhs_rows[4 i + j] += sum_pix R_i sC_j,  rhs_rows[4 j + 3] += sum_pix sC_j            (NULL: not computed)
+ *              -- the exposure rows of J^T b, accumulated into 12 device floats (views sharing a camera add up)
+ * and *loss_dev = [*loss_dev if accumulate] + 2 sum residual^2.  C, seed: products and sums left to right,
+ * uncontracted; with X = [I | 0] residual, weight and seed are bitwise gslm_lm_residual's.  Deterministic (double
+ * block partials, one final pass in fixed order).  scratch >= gslm_exposure_scratch_bytes(H, W). */
+int gslm_lm_residual_exposure(int32_t H, int32_t W, const float* color, const float* gt, const float* alpha_mask,
+                              const float* exposure, float* residual, float* weight, float* seed, float* rhs_rows,
+                              void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate,
+                              void* stream);
 
 /* ---- view-sharded exchange (multi-GPU LM product), SURVEY 8(e) ----
  * Instead of all-reducing the param-space partial J^T W J v (F = 59 floats per Gaussian at SH 3),
