@@ -386,12 +386,14 @@ size_t gslm_loss_scratch_bytes(int32_t H, int32_t W) {
   return (size_t)(ntiles > 0 ? ntiles : 1) * sizeof(double);
 }
 
-int gslm_rasterize_loss(const gslm_view* view, int64_t P, void* geom, void* binning, size_t binning_bytes, int64_t N,
-                        const float* gt, const float* alpha_mask, void* scratch, size_t scratch_bytes, double* loss_dev,
-                        int32_t accumulate, void* stream) {
+// gslm_rasterize_loss and its exposure form: one body, `exposure` NULL for the plain one
+static int rasterize_loss(const gslm_view* view, int64_t P, void* geom, void* binning, size_t binning_bytes, int64_t N,
+                          const float* gt, const float* alpha_mask, const float* exposure, bool want_exposure,
+                          void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate, void* stream) {
   ViewK v;
   int st = make_view(view, 1, &v);
   if (st) return st;
+  if (want_exposure && !exposure) { set_error("rasterize_loss_exposure: NULL exposure"); return GSLM_ERR_INVALID; }
   if (binning_bytes < gslm_binning_bytes(N, v.H, v.W)) { set_error("binning workspace too small"); return GSLM_ERR_CAPACITY; }
   if (scratch_bytes < gslm_loss_scratch_bytes(v.H, v.W)) { set_error("loss scratch too small"); return GSLM_ERR_CAPACITY; }
   if (!gt || !loss_dev || !scratch) { set_error("rasterize_loss: NULL gt / loss / scratch"); return GSLM_ERR_INVALID; }
@@ -401,7 +403,23 @@ int gslm_rasterize_loss(const gslm_view* view, int64_t P, void* geom, void* binn
   bin_layout(N, v.gx * v.gy, binning, &bb);
   hipStream_t s = (hipStream_t)stream;
   if ((st = launch_binning(v, P, gb, bb, N, s))) return st;
-  return launch_render_loss(v, gb, bb, gt, alpha_mask, (double*)scratch, loss_dev, accumulate ? 1 : 0, s);
+  return launch_render_loss(v, gb, bb, gt, alpha_mask, (double*)scratch, loss_dev, accumulate ? 1 : 0, s, nullptr, 0,
+                            nullptr, exposure);
+}
+
+int gslm_rasterize_loss(const gslm_view* view, int64_t P, void* geom, void* binning, size_t binning_bytes, int64_t N,
+                        const float* gt, const float* alpha_mask, void* scratch, size_t scratch_bytes, double* loss_dev,
+                        int32_t accumulate, void* stream) {
+  return rasterize_loss(view, P, geom, binning, binning_bytes, N, gt, alpha_mask, nullptr, false, scratch,
+                        scratch_bytes, loss_dev, accumulate, stream);
+}
+
+int gslm_rasterize_loss_exposure(const gslm_view* view, int64_t P, void* geom, void* binning, size_t binning_bytes,
+                                 int64_t N, const float* gt, const float* alpha_mask, const float* exposure,
+                                 void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate,
+                                 void* stream) {
+  return rasterize_loss(view, P, geom, binning, binning_bytes, N, gt, alpha_mask, exposure, true, scratch,
+                        scratch_bytes, loss_dev, accumulate, stream);
 }
 
 // ---- device-count forms: the pair count stays on the device (no read-back between preprocess and binning) ----
@@ -507,13 +525,15 @@ int gslm_union_binning(const gslm_view* view, int64_t P, const void* union_geom,
   return launch_union_binning(v, P, ug, bb, um, N, u, (hipStream_t)stream);
 }
 
-int gslm_rasterize_loss_slot(const gslm_view* view, int64_t P, const void* geom, size_t set_bytes, const void* binning,
-                             size_t binning_bytes, int64_t N, int32_t slot, int32_t n_sets, const float* gt,
-                             const float* alpha_mask, void* scratch, size_t scratch_bytes, double* loss_dev,
-                             int32_t accumulate, void* stream) {
+static int rasterize_loss_slot(const gslm_view* view, int64_t P, const void* geom, size_t set_bytes,
+                               const void* binning, size_t binning_bytes, int64_t N, int32_t slot, int32_t n_sets,
+                               const float* gt, const float* alpha_mask, const float* exposure, bool want_exposure,
+                               void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate,
+                               void* stream) {
   ViewK v;
   int st = make_view(view, 1, &v);
   if (st) return st;
+  if (want_exposure && !exposure) { set_error("rasterize_loss_slot_exposure: NULL exposure"); return GSLM_ERR_INVALID; }
   if (n_sets < 1 || n_sets > MAX_UNION_SETS || slot < 0 || slot >= n_sets) {
     set_error("rasterize_loss_slot: need 0 <= slot < n_sets <= 8");
     return GSLM_ERR_INVALID;
@@ -531,17 +551,35 @@ int gslm_rasterize_loss_slot(const gslm_view* view, int64_t P, const void* geom,
   bin_layout(N, v.gx * v.gy, const_cast<void*>(binning), &bb);
   union_masks_layout(N, v.gx * v.gy, const_cast<void*>(binning), &um);
   return launch_render_loss(v, gb, bb, gt, alpha_mask, (double*)scratch, loss_dev, accumulate ? 1 : 0,
-                            (hipStream_t)stream, N > 0 ? um.sorted : nullptr, 4 * slot, um.nsets);
+                            (hipStream_t)stream, N > 0 ? um.sorted : nullptr, 4 * slot, um.nsets, exposure);
+}
+
+int gslm_rasterize_loss_slot(const gslm_view* view, int64_t P, const void* geom, size_t set_bytes, const void* binning,
+                             size_t binning_bytes, int64_t N, int32_t slot, int32_t n_sets, const float* gt,
+                             const float* alpha_mask, void* scratch, size_t scratch_bytes, double* loss_dev,
+                             int32_t accumulate, void* stream) {
+  return rasterize_loss_slot(view, P, geom, set_bytes, binning, binning_bytes, N, slot, n_sets, gt, alpha_mask, nullptr,
+                             false, scratch, scratch_bytes, loss_dev, accumulate, stream);
+}
+
+int gslm_rasterize_loss_slot_exposure(const gslm_view* view, int64_t P, const void* geom, size_t set_bytes,
+                                      const void* binning, size_t binning_bytes, int64_t N, int32_t slot,
+                                      int32_t n_sets, const float* gt, const float* alpha_mask, const float* exposure,
+                                      void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate,
+                                      void* stream) {
+  return rasterize_loss_slot(view, P, geom, set_bytes, binning, binning_bytes, N, slot, n_sets, gt, alpha_mask,
+                             exposure, true, scratch, scratch_bytes, loss_dev, accumulate, stream);
 }
 
 size_t gslm_loss_sets_scratch_bytes(int32_t n, int32_t H, int32_t W) {
   return (size_t)(n > 0 ? n : 1) * gslm_loss_scratch_bytes(H, W);
 }
 
-int gslm_rasterize_loss_sets(const gslm_view* view, int64_t P, const void* const* geoms, int32_t n, int32_t first_set,
-                             size_t set_bytes, const void* binning, size_t binning_bytes, int64_t N, const float* gt,
-                             const float* alpha_mask, void* scratch, size_t scratch_bytes, double* const* loss_dev,
-                             int32_t accumulate, void* stream) {
+static int rasterize_loss_sets(const gslm_view* view, int64_t P, const void* const* geoms, int32_t n,
+                               int32_t first_set, size_t set_bytes, const void* binning, size_t binning_bytes,
+                               int64_t N, const float* gt, const float* alpha_mask, const float* const* exposure,
+                               bool want_exposure, void* scratch, size_t scratch_bytes, double* const* loss_dev,
+                               int32_t accumulate, void* stream) {
   ViewK v;
   int st = make_view(view, 1, &v);
   if (st) return st;
@@ -554,10 +592,16 @@ int gslm_rasterize_loss_sets(const gslm_view* view, int64_t P, const void* const
   if (scratch_bytes < gslm_loss_sets_scratch_bytes(n, v.H, v.W)) { set_error("loss scratch too small"); return GSLM_ERR_CAPACITY; }
   if (!gt || !loss_dev || !scratch || !geoms) { set_error("rasterize_loss_sets: NULL gt / loss / scratch / geoms"); return GSLM_ERR_INVALID; }
   if (set_bytes < depth_records_bytes(P)) { set_error("rasterize_loss_sets: set workspace below gslm_depth_records_bytes(P)"); return GSLM_ERR_CAPACITY; }
+  if (want_exposure && !exposure) { set_error("rasterize_loss_sets_exposure: NULL exposure array"); return GSLM_ERR_INVALID; }
   SetRecsK sr{};
   LossPtrsK lp{};
+  ExpPtrsK xp{};
   for (int a = 0; a < n; ++a) {
     if ((P && !geoms[a]) || !loss_dev[a]) { set_error("rasterize_loss_sets: NULL geometry / loss"); return GSLM_ERR_INVALID; }
+    if (want_exposure) {
+      if (!exposure[a]) { set_error("rasterize_loss_sets_exposure: NULL exposure entry"); return GSLM_ERR_INVALID; }
+      xp.x[a] = exposure[a];
+    }
     GeomBufs gb;
     geom_layout(P, const_cast<void*>(geoms[a]), &gb);
     sr.rec[a] = gb.rec;
@@ -569,7 +613,24 @@ int gslm_rasterize_loss_sets(const gslm_view* view, int64_t P, const void* const
   union_masks_layout(N, v.gx * v.gy, const_cast<void*>(binning), &um);
   // um.nsets: slots at or past the set count gslm_union_binning recorded render a NaN loss (as the slot form)
   return launch_render_loss_sets(v, sr, n, bb, um.sorted, gt, alpha_mask, (double*)scratch, lp, accumulate ? 1 : 0,
-                                 (hipStream_t)stream, first_set, um.nsets);
+                                 (hipStream_t)stream, first_set, um.nsets, want_exposure ? &xp : nullptr);
+}
+
+int gslm_rasterize_loss_sets(const gslm_view* view, int64_t P, const void* const* geoms, int32_t n, int32_t first_set,
+                             size_t set_bytes, const void* binning, size_t binning_bytes, int64_t N, const float* gt,
+                             const float* alpha_mask, void* scratch, size_t scratch_bytes, double* const* loss_dev,
+                             int32_t accumulate, void* stream) {
+  return rasterize_loss_sets(view, P, geoms, n, first_set, set_bytes, binning, binning_bytes, N, gt, alpha_mask, nullptr,
+                             false, scratch, scratch_bytes, loss_dev, accumulate, stream);
+}
+
+int gslm_rasterize_loss_sets_exposure(const gslm_view* view, int64_t P, const void* const* geoms, int32_t n,
+                                      int32_t first_set, size_t set_bytes, const void* binning, size_t binning_bytes,
+                                      int64_t N, const float* gt, const float* alpha_mask,
+                                      const float* const* exposure, void* scratch, size_t scratch_bytes,
+                                      double* const* loss_dev, int32_t accumulate, void* stream) {
+  return rasterize_loss_sets(view, P, geoms, n, first_set, set_bytes, binning, binning_bytes, N, gt, alpha_mask,
+                             exposure, true, scratch, scratch_bytes, loss_dev, accumulate, stream);
 }
 
 int gslm_num_rendered_copy(const void* geom, int64_t P, uint32_t* dst, void* stream) {

@@ -516,10 +516,11 @@ int launch_active_list(int64_t P, int64_t N, const GeomBufs& gb, const ScratchBu
                        hipStream_t s);
 int launch_point_ids(const uint32_t* point_list, int64_t N, uint32_t* out, hipStream_t s);
 // amask (or NULL): the blend visits by the union list's per-set masks (bits `shift` .. shift + 3 of amask[k],
-// k_duplicate_union) with the records of gb (that set's geometry) instead of the point list's own quadrant bits
+// k_duplicate_union) with the records of gb (that set's geometry) instead of the point list's own quadrant bits;
+// exposure (or NULL): the camera's 12 device floats, applied to the final colour before the clamp
 int launch_render_loss(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const float* gt, const float* mask,
                        double* part, double* loss, int accumulate, hipStream_t s, const uint32_t* amask = nullptr,
-                       int shift = 0, const uint32_t* nsets = nullptr);
+                       int shift = 0, const uint32_t* nsets = nullptr, const float* exposure = nullptr);
 // ---- the line search's shared binning (forward.hip, gslm_union_*) ----
 constexpr int MAX_UNION_SETS = 8;  // 4 mask bits per set in one uint32 per list entry
 struct UnionSets {
@@ -545,9 +546,13 @@ struct SetRecsK {
 struct LossPtrsK {
   double* loss[MAX_UNION_SETS];
 };
+struct ExpPtrsK {  // per set: its exposure map, 12 device floats (gslm_rasterize_loss_sets_exposure)
+  const float* x[MAX_UNION_SETS];
+};
 int launch_render_loss_sets(const ViewK& v, const SetRecsK& sr, int nsets, const BinBufs& bb, const uint32_t* amask,
                             const float* gt, const float* mask, double* part, const LossPtrsK& lp, int accumulate,
-                            hipStream_t s, int first_set = 0, const uint32_t* nsets_dev = nullptr);
+                            hipStream_t s, int first_set = 0, const uint32_t* nsets_dev = nullptr,
+                            const ExpPtrsK* xp = nullptr);
 int launch_union_rect(int64_t P, const UnionSets& u, const GeomBufs& ug, hipStream_t s);
 int launch_depth_positions(int64_t P, const uint32_t* order, uint32_t* pos, hipStream_t s);
 int launch_union_binning(const ViewK& v, int64_t P, const GeomBufs& ug, const BinBufs& bb, const UnionMasks& um,

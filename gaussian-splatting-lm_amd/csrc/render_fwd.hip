@@ -23,7 +23,10 @@ enum { FWD_FULL = 0, FWD_NO_INV = 1, FWD_LOSS = 2 };
 
 // SLOT (FWD_LOSS only): the line search's union list (gslm_rasterize_loss_slot) -- an entry is visited by its set's
 // bits of amask (k_slot_masks: the set's own quadrant mask, 0 outside the set's rect) instead of the point list's.
-template <int MODE, bool SLOT = false>
+// EXPO (FWD_LOSS only): the trained exposure's loss (gslm_rasterize_loss_exposure) -- the pixel's final colour goes
+// through the camera's 3x4 affine map X (12 device floats, wave-uniform) before the clamp, k_lm_residual_exposure's
+// arithmetic in its order.  X is read after the blend loop, which is the same loop with the same registers.
+template <int MODE, bool SLOT = false, bool EXPO = false>
 __global__ __launch_bounds__(256) void k_render_fwd_wave(ViewK v, const uint2* __restrict__ ranges,
                                                           const uint32_t* __restrict__ tile_order,
                                                           const uint32_t* __restrict__ point_list,
@@ -31,7 +34,9 @@ __global__ __launch_bounds__(256) void k_render_fwd_wave(ViewK v, const uint2* _
                                                           float* __restrict__ out_invdepth, float* __restrict__ final_T,
                                                           uint32_t* __restrict__ n_contrib, const float* __restrict__ gt,
                                                           const float* __restrict__ mask, double* __restrict__ part,
-                                                          const uint32_t* __restrict__ amask = nullptr, int shift = 0) {
+                                                          const uint32_t* __restrict__ amask = nullptr, int shift = 0,
+                                                          const float* __restrict__ X = nullptr) {
+  static_assert(!EXPO || MODE == FWD_LOSS, "the exposure map belongs to the loss epilogue");
   __shared__ float4 s_rec[4][3 * 64];
   const int tile = (int)tile_order[blockIdx.x];
   const int tile_x = tile % v.gx, tile_y = tile / v.gx;
@@ -107,9 +112,16 @@ __global__ __launch_bounds__(256) void k_render_fwd_wave(ViewK v, const uint2* _
     if (inside) {
       const float m = mask ? mask[pid] : 1.0f;
       const float R[3] = {C0 + T * v.bg[0], C1 + T * v.bg[1], C2 + T * v.bg[2]};
+      float x[12];
+      if constexpr (EXPO) {
+#pragma unroll
+        for (int k = 0; k < 12; ++k) x[k] = X[k];  // wave-uniform
+      }
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const float r = m * clamp01(R[c]) - gt[c * HW + pid];
+        // a lane outside the image never gets here: with an offset column its exposed colour would not be 0
+        const float Cc = EXPO ? ((R[0] * x[c] + R[1] * x[4 + c]) + R[2] * x[8 + c]) + x[4 * c + 3] : R[c];
+        const float r = m * clamp01(Cc) - gt[c * HW + pid];
         acc += (double)r * (double)r;
       }
     }
@@ -134,13 +146,15 @@ __global__ __launch_bounds__(256) void k_render_fwd_wave(ViewK v, const uint2* _
 // visit arithmetic on set a's own pixel state, the same per-set stop.  Set a + 1's records are loaded while set a's
 // hits are visited, so a round waits on two dependent loads (entries, set 0's records) instead of two per set.
 // Every set's visits and their order are the single-set kernel's: the same losses, bitwise.
-template <int NS>
+// EXPO: set a's final colour goes through its own exposure map xp.x[a] (k_render_fwd_wave's EXPO epilogue), read
+// after the list walk and indexed by the unrolled set number only.
+template <int NS, bool EXPO = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS <= 6 ? 8 : 1))) void k_render_loss_sets(ViewK v, const uint2* __restrict__ ranges,
                                                            const uint32_t* __restrict__ tile_order,
                                                            const uint32_t* __restrict__ point_list,
                                                            const uint32_t* __restrict__ amask, SetRecsK sr,
                                                            const float* __restrict__ gt, const float* __restrict__ mask,
-                                                           double* __restrict__ part, int shift) {
+                                                           double* __restrict__ part, int shift, ExpPtrsK xp) {
   __shared__ float4 s_rec[4][3 * 64];
   const int tile = (int)tile_order[blockIdx.x];
   const int tile_x = tile % v.gx, tile_y = tile / v.gx;
@@ -246,9 +260,16 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS <= 6 ? 8
     if (inside) {
       const float Tf = T[a] > 0.0f ? T[a] : -T[a];
       const float R[3] = {C0[a] + Tf * v.bg[0], C1[a] + Tf * v.bg[1], C2[a] + Tf * v.bg[2]};
+      float x[12];
+      if constexpr (EXPO) {
+        const float* __restrict__ X = xp.x[a];
+#pragma unroll
+        for (int k = 0; k < 12; ++k) x[k] = X[k];  // wave-uniform
+      }
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
-        const float r = mv * clamp01(R[c]) - gtc[c];
+        const float Cc = EXPO ? ((R[0] * x[c] + R[1] * x[4 + c]) + R[2] * x[8 + c]) + x[4 * c + 3] : R[c];
+        const float r = mv * clamp01(Cc) - gtc[c];
         acc += (double)r * (double)r;
       }
     }
@@ -283,7 +304,7 @@ __global__ __launch_bounds__(256) void k_tile_loss_final_sets(const double* __re
 
 int launch_render_loss_sets(const ViewK& v, const SetRecsK& sr, int nsets, const BinBufs& bb, const uint32_t* amask,
                             const float* gt, const float* mask, double* part, const LossPtrsK& lp, int accumulate,
-                            hipStream_t s, int first_set, const uint32_t* nsets_dev) {
+                            hipStream_t s, int first_set, const uint32_t* nsets_dev, const ExpPtrsK* xp) {
   const int ntiles = v.gx * v.gy;
   if (ntiles == 0) {
     if (!accumulate)
@@ -291,11 +312,16 @@ int launch_render_loss_sets(const ViewK& v, const SetRecsK& sr, int nsets, const
     return GSLM_OK;
   }
   const dim3 grid(ntiles), block(TILE_PIX);
+  const ExpPtrsK x = xp ? *xp : ExpPtrsK{};
   switch (nsets) {
-#define GSLM_LOSS_SETS(NS)                                                                                           \
-  case NS:                                                                                                           \
-    hipLaunchKernelGGL(k_render_loss_sets<NS>, grid, block, 0, s, v, bb.ranges, bb.tile_order, bb.point_list, amask, \
-                       sr, gt, mask, part, 4 * first_set);                                                           \
+#define GSLM_LOSS_SETS(NS)                                                                                          \
+  case NS:                                                                                                          \
+    if (xp)                                                                                                         \
+      hipLaunchKernelGGL((k_render_loss_sets<NS, true>), grid, block, 0, s, v, bb.ranges, bb.tile_order,            \
+                         bb.point_list, amask, sr, gt, mask, part, 4 * first_set, x);                               \
+    else                                                                                                            \
+      hipLaunchKernelGGL((k_render_loss_sets<NS, false>), grid, block, 0, s, v, bb.ranges, bb.tile_order,           \
+                         bb.point_list, amask, sr, gt, mask, part, 4 * first_set, x);                               \
     break;
     GSLM_LOSS_SETS(1) GSLM_LOSS_SETS(2) GSLM_LOSS_SETS(3) GSLM_LOSS_SETS(4)
     GSLM_LOSS_SETS(5) GSLM_LOSS_SETS(6) GSLM_LOSS_SETS(7) GSLM_LOSS_SETS(8)
@@ -335,31 +361,39 @@ int launch_render_fwd(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, con
   if (out_invdepth)
     hipLaunchKernelGGL((k_render_fwd_wave<FWD_FULL, false>), dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges, bb.tile_order,
                        bb.point_list, gb.rec, out_color, out_invdepth, ib.final_T, ib.n_contrib, (const float*)nullptr,
-                       (const float*)nullptr, (double*)nullptr, (const uint32_t*)nullptr, 0);
+                       (const float*)nullptr, (double*)nullptr, (const uint32_t*)nullptr, 0, (const float*)nullptr);
   else
     hipLaunchKernelGGL((k_render_fwd_wave<FWD_NO_INV, false>), dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges, bb.tile_order,
                        bb.point_list, gb.rec, out_color, (float*)nullptr, ib.final_T, ib.n_contrib, (const float*)nullptr,
-                       (const float*)nullptr, (double*)nullptr, (const uint32_t*)nullptr, 0);
+                       (const float*)nullptr, (double*)nullptr, (const uint32_t*)nullptr, 0, (const float*)nullptr);
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
 }
 
 int launch_render_loss(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const float* gt, const float* mask,
                        double* part, double* loss, int accumulate, hipStream_t s, const uint32_t* amask, int shift,
-                       const uint32_t* nsets) {
+                       const uint32_t* nsets, const float* exposure) {
   const int ntiles = v.gx * v.gy;
   if (ntiles == 0) {
     if (!accumulate) GSLM_HIP_CHECK(hipMemsetAsync(loss, 0, sizeof(double), s));
     return GSLM_OK;
   }
-  if (amask)
+  if (exposure && amask)
+    hipLaunchKernelGGL((k_render_fwd_wave<FWD_LOSS, true, true>), dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges,
+                       bb.tile_order, bb.point_list, gb.rec, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                       (uint32_t*)nullptr, gt, mask, part, amask, shift, exposure);
+  else if (exposure)
+    hipLaunchKernelGGL((k_render_fwd_wave<FWD_LOSS, false, true>), dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges,
+                       bb.tile_order, bb.point_list, gb.rec, (float*)nullptr, (float*)nullptr, (float*)nullptr,
+                       (uint32_t*)nullptr, gt, mask, part, (const uint32_t*)nullptr, 0, exposure);
+  else if (amask)
     hipLaunchKernelGGL((k_render_fwd_wave<FWD_LOSS, true>), dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges,
                        bb.tile_order, bb.point_list, gb.rec, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                       (uint32_t*)nullptr, gt, mask, part, amask, shift);
+                       (uint32_t*)nullptr, gt, mask, part, amask, shift, (const float*)nullptr);
   else
     hipLaunchKernelGGL((k_render_fwd_wave<FWD_LOSS, false>), dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges,
                        bb.tile_order, bb.point_list, gb.rec, (float*)nullptr, (float*)nullptr, (float*)nullptr,
-                       (uint32_t*)nullptr, gt, mask, part, (const uint32_t*)nullptr, 0);
+                       (uint32_t*)nullptr, gt, mask, part, (const uint32_t*)nullptr, 0, (const float*)nullptr);
   hipLaunchKernelGGL(k_tile_loss_final, dim3(1), dim3(256), 0, s, (const double*)part, ntiles, accumulate, loss,
                      amask ? nsets : nullptr, shift / 4);
   GSLM_LAUNCH_CHECK();

@@ -170,6 +170,25 @@ EXPORTS = {
                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p,
                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
                                                 ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32, ctypes.c_void_p]),
+    # the loss blends under a trained exposure: the plain forms with `exposure` after alpha_mask
+    "gslm_rasterize_loss_exposure": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int64, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p,
+                                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                    ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    "gslm_rasterize_loss_slot_exposure": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int64, ctypes.c_void_p,
+                                                         ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                                         ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                         ctypes.c_int32, ctypes.c_void_p]),
+    "gslm_rasterize_loss_sets_exposure": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int64,
+                                                         ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
+                                                         ctypes.c_int32, ctypes.c_size_t, ctypes.c_void_p,
+                                                         ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p,
+                                                         ctypes.c_void_p, ctypes.POINTER(ctypes.c_void_p),
+                                                         ctypes.c_void_p, ctypes.c_size_t,
+                                                         ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
+                                                         ctypes.c_void_p]),
     "gslm_forward": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.POINTER(GslmGaussians), ctypes.c_void_p,
                                     ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                     ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -1501,13 +1501,22 @@ class LossEvaluator:
     same).  `reduce`: a callable summing it over the ranks that hold the other views (gslm.parallel.allreduce_loss)."""
 
     def __init__(self, model, cams, bg, device="cuda", batch=8, gts=None, alpha_masks=None, reduce=None, streams=3,
-                 device_count=False, train_exposure=False):
+                 device_count=False, train_exposure=False, fused_exposure=False):
         """train_exposure: the loss is taken on the exposed colour of each camera's row of model._exposure, as
         LMProblem(train_exposure=True) takes it: 2 sum ||m clamp01(C) - gt||^2.  evaluate() then renders each view
         with the full forward and runs gslm_lm_residual_exposure in its loss-only mode (no fused loss epilogue, no
-        side streams); evaluate_points -- the union line search -- renders no exposure and raises ValueError."""
+        side streams), and evaluate_points -- the union line search -- raises ValueError.
+        fused_exposure (with train_exposure, without device_count -- else ValueError): the exposure is applied in the
+        blend's loss epilogue instead (gslm_rasterize_loss_exposure: the same per-pixel residuals, summed per tile).
+        evaluate() then takes its ordinary path -- batches, side streams, cached depth orders -- and evaluate_points
+        is allowed: every set carries its own _exposure, and view i at set a uses row exp_idx[i] of it."""
         self.model = model
         self.train_exposure = bool(train_exposure)
+        self.fused_exposure = bool(fused_exposure)
+        if self.fused_exposure and not self.train_exposure:
+            raise ValueError("fused_exposure=True is an option of train_exposure=True")
+        if self.fused_exposure and device_count:
+            raise ValueError("fused_exposure=True: the device-count blend has no exposure form (device_count=False)")
         if self.train_exposure:
             if getattr(model, "pretrained_exposures", None) is not None:
                 raise ValueError("train_exposure: the model renders with pretrained exposures, which are not parameters")
@@ -1515,6 +1524,7 @@ class LossEvaluator:
             if missing:
                 raise ValueError(f"train_exposure: no row of model._exposure for {missing} (model.exposure_mapping)")
             self.exp_idx = [int(model.exposure_mapping[c.image_name]) for c in cams]
+        if self.train_exposure and not self.fused_exposure:
             self._exp_scratch = torch.empty(lib.gslm_exposure_scratch_bytes(1, 1) // 8, dtype=torch.float64,
                                             device=device)
             self._exp_raster = {}  # (H, W) -> the ViewRaster whose workspaces the views of that size share
@@ -1568,6 +1578,32 @@ class LossEvaluator:
         st = self.streams[k % len(self.streams)]
         return st, (st.cuda_stream if st is not None else _lib.stream_handle(self.device))
 
+    def _exposure_rows(self, holder, what="model"):
+        """holder._exposure checked for the kernels (contiguous float32 [n, 3, 4] on the device): its data pointer;
+        camera row r is the 12 floats at + 48 r."""
+        X = getattr(holder, "_exposure", None)
+        ref = self.model._exposure
+        if (not torch.is_tensor(X) or X.dtype != torch.float32 or not X.is_contiguous() or X.shape != ref.shape
+                or tuple(X.shape[1:]) != (3, 4) or X.device.type != torch.device(self.device).type):
+            raise ValueError(f"fused_exposure: {what}._exposure must be contiguous float32 {tuple(ref.shape)} on "
+                             f"{self.device}")
+        return X.data_ptr()
+
+    def _blend_loss(self, vw, P, sl, N, i, xrows, scr, out, sh):
+        """gslm_rasterize_loss of view i from slot sl into the double at `out`; xrows (fused_exposure): the data
+        pointer of the exposure rows, the blend then gslm_rasterize_loss_exposure with the camera's row."""
+        m = self.masks[i]
+        mp = None if m is None else m.data_ptr()
+        if xrows is None:
+            check(lib.gslm_rasterize_loss(ctypes.byref(vw), P, sl["geom"].data_ptr(), sl["binning"].data_ptr(),
+                                          sl["binning"].numel(), N, self.gts[i].data_ptr(), mp, scr.data_ptr(),
+                                          scr.numel() * 8, out, 0, sh), "gslm_rasterize_loss")
+        else:
+            check(lib.gslm_rasterize_loss_exposure(ctypes.byref(vw), P, sl["geom"].data_ptr(), sl["binning"].data_ptr(),
+                                                   sl["binning"].numel(), N, self.gts[i].data_ptr(), mp,
+                                                   xrows + 48 * self.exp_idx[i], scr.data_ptr(), scr.numel() * 8, out,
+                                                   0, sh), "gslm_rasterize_loss_exposure")
+
     def _render_exact(self, g, i, losses):
         """View i's loss into losses[i] with the count read back first (slot 0 grown as needed; main stream)."""
         P = g.P
@@ -1583,17 +1619,14 @@ class LossEvaluator:
         need = lib.gslm_binning_bytes(N, vw.image_height, vw.image_width)
         if sl["binning"] is None or sl["binning"].numel() < need:
             sl["binning"] = _lib.u8(int(need * 1.25) + 4096, self.device)
-        m = self.masks[i]
-        scr = self.loss_scratch[0]
-        check(lib.gslm_rasterize_loss(ctypes.byref(vw), P, sl["geom"].data_ptr(), sl["binning"].data_ptr(),
-                                      sl["binning"].numel(), N, self.gts[i].data_ptr(), None if m is None else m.data_ptr(),
-                                      scr.data_ptr(), scr.numel() * 8, losses.data_ptr() + 8 * i, 0, main_h),
-              "gslm_rasterize_loss")
+        self._blend_loss(vw, P, sl, N, i, None, self.loss_scratch[0], losses.data_ptr() + 8 * i, main_h)
 
     def evaluate(self):
         """Device double: the loss over this evaluator's views (summed over the ranks with `reduce`)."""
-        if self.train_exposure:
+        if self.train_exposure and not self.fused_exposure:
             return self._evaluate_exposure()
+        # fused_exposure: the blends read the cameras' rows of model._exposure on the device, in stream order
+        xrows = self._exposure_rows(self.model) if self.fused_exposure else None
         g = raw_gaussians(self.model)
         P = g.P
         V = len(self.views)
@@ -1661,12 +1694,8 @@ class LossEvaluator:
                     if sl["binning"] is not None and st is not None:
                         main.wait_stream(st)  # the old buffer is freed on the main stream: after its last use
                     sl["binning"] = _lib.u8(int(need * 1.25) + 4096, self.device)
-                m = self.masks[i]
-                scr = self.loss_scratch[k % len(self.streams)]
-                check(lib.gslm_rasterize_loss(ctypes.byref(vw), P, sl["geom"].data_ptr(), sl["binning"].data_ptr(),
-                                              sl["binning"].numel(), N, self.gts[i].data_ptr(),
-                                              None if m is None else m.data_ptr(), scr.data_ptr(), scr.numel() * 8,
-                                              losses.data_ptr() + 8 * i, 0, sh), "gslm_rasterize_loss")
+                self._blend_loss(vw, P, sl, N, i, xrows, self.loss_scratch[k % len(self.streams)],
+                                 losses.data_ptr() + 8 * i, sh)
         for st in self.streams:
             if st is not None:
                 main.wait_stream(st)
@@ -1764,15 +1793,18 @@ class LossEvaluator:
         (gslm_preprocess_views with the view's depth positions: one pass over the Gaussians per set for the batch's
         views), ONE binning over the union of the sets' rects (gslm_union_geometry / gslm_union_binning: 4 mask bits
         per set and list entry, carried through the tile sort), then the n blends + losses through it
-        (gslm_rasterize_loss_slot).
+        (gslm_rasterize_loss_slot).  With fused_exposure every set also carries its _exposure (param_snapshot(model,
+        exposure=True)) and the blends are the exposure forms, view i at set a under row exp_idx[i] of sets[a]._exposure.
         Pipelining: a batch's preprocesses, union geometries and pair-count read-back run on the main stream while the
         previous batch's binnings and blends run on the side streams (two alternating slot sets), so the read-back does
         not drain the device.  union_counts[i]: view i's union list length (the last call)."""
-        if self.train_exposure:
-            raise ValueError("evaluate_points renders no exposure: with train_exposure the line search is exact")
+        if self.train_exposure and not self.fused_exposure:
+            raise ValueError("evaluate_points renders no exposure: with train_exposure the line search is exact "
+                             "(fused_exposure=True renders it in the blend's epilogue)")
         n = len(sets)
         if not 1 <= n <= 8:
             raise ValueError("evaluate_points takes 1..8 parameter sets")
+        xs = [self._exposure_rows(st, f"sets[{a}]") for a, st in enumerate(sets)] if self.fused_exposure else None
         xyz = sets[0]._xyz
         if any(st._xyz is not xyz for st in sets):
             raise ValueError("evaluate_points: every set shares the frozen xyz tensor")
@@ -1849,6 +1881,8 @@ class LossEvaluator:
                 check(lib.gslm_union_binning(ctypes.byref(vw), P, sl["ugeom"].data_ptr(), binning.data_ptr(),
                                              binning.numel(), N, ge, n, sb, sh), "gslm_union_binning")
                 m = self.masks[i]
+                mp = None if m is None else m.data_ptr()
+                xoff = 48 * self.exp_idx[i] if xs is not None else 0
                 if self.loss_sets > 1:  # groups of loss_sets sets, one pass over the union list each
                     gsz = min(self.loss_sets, n)
                     scr = self._sets_scratch(k, gsz, H, W)
@@ -1856,6 +1890,13 @@ class LossEvaluator:
                         na = min(gsz, n - a0)
                         gg = (ctypes.c_void_p * na)(*[sl["geoms"][a].data_ptr() for a in range(a0, a0 + na)])
                         lp = (ctypes.c_void_p * na)(*[losses[a].data_ptr() + 8 * i for a in range(a0, a0 + na)])
+                        if xs is not None:
+                            xp = (ctypes.c_void_p * na)(*[xs[a] + xoff for a in range(a0, a0 + na)])
+                            check(lib.gslm_rasterize_loss_sets_exposure(
+                                ctypes.byref(vw), P, gg, na, a0, sb, binning.data_ptr(), binning.numel(), N,
+                                self.gts[i].data_ptr(), mp, xp, scr.data_ptr(), scr.numel() * 8, lp, 0, sh),
+                                "gslm_rasterize_loss_sets_exposure")
+                            continue
                         check(lib.gslm_rasterize_loss_sets(ctypes.byref(vw), P, gg, na, a0, sb, binning.data_ptr(),
                                                            binning.numel(), N, self.gts[i].data_ptr(),
                                                            None if m is None else m.data_ptr(), scr.data_ptr(),
@@ -1863,6 +1904,12 @@ class LossEvaluator:
                     continue
                 scr = self.loss_scratch[k % len(self.streams)]
                 for a in range(n):
+                    if xs is not None:
+                        check(lib.gslm_rasterize_loss_slot_exposure(
+                            ctypes.byref(vw), P, sl["geoms"][a].data_ptr(), sb, binning.data_ptr(), binning.numel(), N,
+                            a, n, self.gts[i].data_ptr(), mp, xs[a] + xoff, scr.data_ptr(), scr.numel() * 8,
+                            losses[a].data_ptr() + 8 * i, 0, sh), "gslm_rasterize_loss_slot_exposure")
+                        continue
                     check(lib.gslm_rasterize_loss_slot(ctypes.byref(vw), P, sl["geoms"][a].data_ptr(), sb,
                                                        binning.data_ptr(), binning.numel(), N, a, n, self.gts[i].data_ptr(),
                                                        None if m is None else m.data_ptr(), scr.data_ptr(),
@@ -1889,14 +1936,15 @@ class LossEvaluator:
 _LS_GROUPS = ("_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity")
 
 
-def param_snapshot(model):
+def param_snapshot(model, exposure=False):
     """A line-search point's parameters for LossEvaluator.evaluate_points: clones of the groups the LM step moves,
-    the model's own (frozen) xyz tensor.  The exposure group is not part of a snapshot: evaluate_points renders no
-    exposure, so lm_step(train_exposure=True) searches in the exact order instead."""
+    the model's own (frozen) xyz tensor.  exposure=True also clones model._exposure, for an evaluator with
+    fused_exposure (lm_step(train_exposure=True, val_exposure="fused")); without it the exposure group is not part
+    of a snapshot."""
     import types
     ns = types.SimpleNamespace(_xyz=model._xyz, active_sh_degree=model.active_sh_degree)
     with torch.no_grad():
-        for k in _LS_GROUPS:
+        for k in _LS_GROUPS + (("_exposure",) if exposure else ()):
             setattr(ns, k, getattr(model, k).detach().clone())
     return ns
 
@@ -1929,7 +1977,7 @@ def clear_val_cache():
 def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, mask_xyz=True, check_every=True,
             verbose=False, device="cuda", sh_projection="auto", recursion="fused", exchange="auto", group=None,
             val_batch=8, timing=False, backend=None, line_search="union", val_at_start=False, cache_val=True,
-            multiview="loop", union_active=False, train_exposure=False):
+            multiview="loop", union_active=False, train_exposure=False, val_exposure="forward"):
     """One LM step of train_jvp.py:237-289: loss, CGLS on the normal equations, backtracking line search.
 
     Single process: LMProblem over `cams` (with one training view the SH-rest group of the CG vectors is carried
@@ -1958,9 +2006,14 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     training view can move (BatchedLMProblem(union_active=True)); off by default.
     train_exposure: the step also moves the exposure rows of the training cameras (LMProblem(train_exposure=True)),
     and the validation loss is taken under each validation camera's exposure (LossEvaluator(train_exposure=True)).
-    The line search then runs in the exact order (the union evaluator renders no exposure).  Single process,
-    multiview="loop", recursion="fused", mask_xyz=True -- anything else raises ValueError.  Off by default: nothing
-    changes, and model._exposure is not touched.
+    Single process, multiview="loop", recursion="fused", mask_xyz=True -- anything else raises ValueError.  Off by
+    default: nothing changes, and model._exposure is not touched.
+    val_exposure (train_exposure=True only; any other string, or "fused" without it, raises ValueError): "forward"
+    renders each validation view with the full forward and takes the exposure residual's loss of the image, one view
+    after the other, and the line search runs in the exact order whatever line_search says.  "fused" applies the
+    exposure in the loss blend's epilogue (LossEvaluator(fused_exposure=True)): the validation runs in batches over the
+    side streams, and line_search="union" snapshots the six points with their exposure and evaluates them through one
+    binning per view; line_search="exact" runs the fused evaluation seven times.
     backend: (problem_cls, evaluator_cls, solver) replacing (LMProblem, LossEvaluator, cgls_fused) -- the CPU
     multi-process tests run this same driver, sharding and reductions on the oracle restatement."""
     import time
@@ -1981,7 +2034,12 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     if train_exposure and (sharded or multiview != "loop" or recursion != "fused" or not mask_xyz):
         raise ValueError("train_exposure=True is the single-process step with multiview='loop', recursion='fused' "
                          "and mask_xyz=True")
+    if val_exposure not in ("forward", "fused"):
+        raise ValueError(f"val_exposure must be 'forward' or 'fused', got {val_exposure!r}")
+    if val_exposure == "fused" and not train_exposure:
+        raise ValueError("val_exposure='fused' is an option of train_exposure=True")
     exp_kw = {"train_exposure": True} if train_exposure else {}
+    fused_exposure = val_exposure == "fused"
     t = {}
     clock = [time.perf_counter()]
 
@@ -2030,7 +2088,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     # next while the model, the validation cameras (held by it, so their ids stay theirs) and the settings are the same
     imgs = [(getattr(c, "original_image", None), getattr(c, "alpha_mask", None)) for c in mine_val]
     vkey = (id(model), model.active_sh_degree, tuple(id(c) for c in mine_val), tuple(id(t) for p in imgs for t in p),
-            str(device), val_batch, evaluator_cls, sharded, id(group), bool(train_exposure),
+            str(device), val_batch, evaluator_cls, sharded, id(group), bool(train_exposure), val_exposure,
             tuple(float(x) for x in torch.as_tensor(bg).reshape(-1).tolist()))
     hit = _VAL_CACHE.get("last") if cache_val else None
     if hit is not None and hit[0] == vkey:
@@ -2041,6 +2099,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
         _VAL_CACHE.pop("last", None)
         val = evaluator_cls(model, mine_val, bg, device=device, batch=val_batch,
                             reduce=(lambda x: allreduce_loss(x, group)) if sharded else None, **exp_kw,
+                            **({"fused_exposure": True} if fused_exposure else {}),
                             # (GSLM_VAL_STREAMS: the side-stream count, an A/B override of LossEvaluator's default)
                             **({"streams": int(os.environ["GSLM_VAL_STREAMS"])} if "GSLM_VAL_STREAMS" in os.environ else {}))
         if cache_val:
@@ -2051,7 +2110,8 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
         lap("val_start_ms")
     if line_search not in ("union", "exact"):
         raise ValueError(f"line_search must be 'union' or 'exact', got {line_search!r}")
-    union = line_search == "union" and mask_xyz and hasattr(val, "evaluate_points") and not train_exposure
+    union = (line_search == "union" and mask_xyz and hasattr(val, "evaluate_points")
+             and (fused_exposure or not train_exposure))
     # train_jvp.py:262-279: alpha = 2, 1, ..., 1/16 on the validation views, keep the best, step to it
     alpha = 2.0
     best_alpha, best_loss = alpha, math.inf
@@ -2061,7 +2121,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
         # the same update_step sequence, the six points' parameters kept; their losses from one binning per view
         points = []
         for _ in range(6):
-            points.append((alpha, param_snapshot(model)))
+            points.append((alpha, param_snapshot(model, exposure=fused_exposure)))
             new_alpha = alpha * 0.5
             update_params(model, full, s, new_alpha - alpha, skip_xyz=mask_xyz)
             alpha = new_alpha

@@ -211,6 +211,29 @@ int gslm_rasterize_loss_sets(const gslm_view* view, int64_t P, const void* const
                              size_t set_bytes, const void* binning, size_t binning_bytes, int64_t num_rendered,
                              const float* gt, const float* alpha_mask, void* scratch, size_t scratch_bytes,
                              double* const* loss_dev, int32_t accumulate, void* stream);
+/* The three loss blends under a trained per-camera exposure (still ABI 9, additive): the plain form's arguments,
+ * checks, scratch sizes and per-tile sums, with the pixel's final colour R = C + T bg mapped through the camera's
+ * exposure X before the clamp -- gslm_lm_residual_exposure's arithmetic in its order, so the per-pixel residuals are
+ * that function's floats on gslm_rasterize's image:
+ *   C'_j = ((R_0 X[j] + R_1 X[4 + j]) + R_2 X[8 + j]) + X[4 j + 3],   r_j = m clamp(C'_j, 0, 1) - gt_j.
+ * exposure: 12 device floats (the model's [3, 4] row of the view's camera), read by the kernel in stream order -- no
+ * host read; X = [I | 0] gives the plain form's loss bitwise.  gslm_rasterize_loss_sets_exposure takes a host array of
+ * n device pointers, entry a belonging to slot first_set + a (each set its own X).  A NULL exposure, or a NULL entry
+ * of the array, returns GSLM_ERR_INVALID before any launch.  The device-count form has no exposure variant. */
+int gslm_rasterize_loss_exposure(const gslm_view* view, int64_t P, void* geom, void* binning, size_t binning_bytes,
+                                 int64_t num_rendered, const float* gt, const float* alpha_mask, const float* exposure,
+                                 void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate,
+                                 void* stream);
+int gslm_rasterize_loss_slot_exposure(const gslm_view* view, int64_t P, const void* geom, size_t set_bytes,
+                                      const void* binning, size_t binning_bytes, int64_t num_rendered, int32_t slot,
+                                      int32_t n_sets, const float* gt, const float* alpha_mask, const float* exposure,
+                                      void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate,
+                                      void* stream);
+int gslm_rasterize_loss_sets_exposure(const gslm_view* view, int64_t P, const void* const* geoms, int32_t n,
+                                      int32_t first_set, size_t set_bytes, const void* binning, size_t binning_bytes,
+                                      int64_t num_rendered, const float* gt, const float* alpha_mask,
+                                      const float* const* exposure, void* scratch, size_t scratch_bytes,
+                                      double* const* loss_dev, int32_t accumulate, void* stream);
 /* Convenience: gslm_preprocess + gslm_num_rendered + gslm_rasterize.  If binning_bytes is too
  * small returns GSLM_ERR_CAPACITY with *out_num_rendered set (geometry is valid: call
  * gslm_rasterize with a larger buffer). */
