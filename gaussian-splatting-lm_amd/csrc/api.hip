@@ -1146,6 +1146,18 @@ int gslm_inspect_rowmap(const void* geom, int64_t P, int64_t N, const void* scra
   return GSLM_OK;
 }
 
+int gslm_inspect_list(const void* binning, size_t binning_bytes, int64_t N, int32_t H, int32_t W, uint32_t* words,
+                      uint32_t* slots, void* stream) {
+  if (N < 0 || H <= 0 || W <= 0 || !binning) { set_error("inspect_list: NULL binning, negative count or empty image"); return GSLM_ERR_INVALID; }
+  if (binning_bytes < gslm_binning_bytes(N, H, W)) { set_error("inspect_list: binning workspace too small"); return GSLM_ERR_CAPACITY; }
+  BinBufs bb;
+  bin_layout(N, ((W + TILE_X - 1) / TILE_X) * ((H + TILE_Y - 1) / TILE_Y), const_cast<void*>(binning), &bb);
+  hipStream_t s = (hipStream_t)stream;
+  if (words && N > 0) GSLM_HIP_CHECK(hipMemcpyAsync(words, bb.point_list, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
+  if (slots && N > 0) GSLM_HIP_CHECK(hipMemcpyAsync(slots, bb.slots, (size_t)N * 4, hipMemcpyDeviceToDevice, s));
+  return GSLM_OK;
+}
+
 int gslm_active_pack(const float* src, float* dst, const int32_t* active_ids, int64_t n_active, int64_t P,
                      const int32_t* widths, int32_t ngroups, int64_t tail_n, void* stream) {
   return launch_active_pack(true, src, dst, active_ids, n_active, P, widths, ngroups, tail_n, (hipStream_t)stream);

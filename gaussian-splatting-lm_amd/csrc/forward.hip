@@ -11,6 +11,7 @@
 //   (k_render_fwd, the per-tile blend: render_fwd.hip)
 #include "gslm_internal.hpp"
 #include "gslm_kernels.hpp"
+#include "gslm_tile.hpp"
 
 namespace gslm {
 
@@ -598,6 +599,82 @@ __global__ __launch_bounds__(256) void k_tile_cost(const uint2* __restrict__ ran
   if (tid == 0) cost[tile] = max(max(tot[0], tot[1]), max(tot[2], tot[3])) + vjp;
 }
 
+// GSLM_LIVE_MASKS=0 (A/B): the row map on the binning's own quadrant masks, without k_quad_live.  Read at every row
+// map, once per geometry (gslm.lm.live_masks validates the value).
+static bool live_masks_on() {
+  const char* e = getenv("GSLM_LIVE_MASKS");
+  return !(e && std::string(e) == "0");
+}
+
+// Refines the list's quadrant masks to the visits some pixel blends.  The binning's mask bit q of an entry says its
+// alpha region can reach quadrant q (quad_mask: conservative); whether any pixel of the quadrant blends it -- inside
+// the image, list position below its n_contrib, !(power > 0), alpha >= 1/255 -- depends on the geometry only, which
+// is fixed from one forward to the next: rhs(), every CG iteration, every restart.  A visit that no lane blends
+// runs no body in the J v pass and stores a zero partial in the VJP pass, so with its bit cleared both skip it and
+// compute the same bits; an entry left with an empty mask is no head (k_row_flags) and owns no row.
+// One block per tile, one independent wave per quadrant, in the shape of jvp_wave_packed: 64 list positions per
+// round, only the wave's hits below its bound neff[q], the primal half of the record (position, conic, opacity) in
+// the wave's own LDS slots, power and alpha exactly as jvp_wave_packed and vjp_tile compute them (gpower, gexp,
+// fminf(0.99f, o G), uncontracted).  The lane that fetched a hit no lane blends clears bit q of that entry:
+// an integer atomic AND, each of the tile's four waves owning one bit of the word.  Nothing else in the entry
+// changes, and positions at or past neff[q] are left alone (every consumer masks them by the same bound).
+// Idempotent: a cleared bit is no hit and a live visit stays live, so a row map rebuilt on one binning
+// (launch_lm_rowmap once per product kind) refines nothing further.
+__global__ __launch_bounds__(256) void k_quad_live(ViewK v, const uint2* __restrict__ ranges,
+                                                    const uint32_t* __restrict__ tile_order,
+                                                    const uint32_t* __restrict__ neff,
+                                                    const float4* __restrict__ rec,
+                                                    const uint32_t* __restrict__ n_contrib, uint32_t* point_list) {
+  __shared__ float4 s_a[4][64];  // [wave][lane]: x, y, conic a, conic b
+  __shared__ float2 s_b[4][64];  //               conic c, opacity
+  const int tile = (int)tile_order[blockIdx.x];
+  const int tile_x = tile % v.gx, tile_y = tile / v.gx;
+  const int tid = threadIdx.x, q = tid >> 6, lane = tid & 63;
+  int px, py;
+  tile_pixel(tile_x, tile_y, tid, px, py);
+  const bool inside = px < v.W && py < v.H;
+  const uint32_t my_last = inside ? n_contrib[(int64_t)py * v.W + px] : 0u;
+  const uint2 range = ranges[tile];
+  const int wm = __builtin_amdgcn_readfirstlane((int)min(neff[4 * tile + q], range.y - range.x));
+  const float pxf = (float)px, pyf = (float)py;
+  uint32_t* pl = point_list + range.x;
+  float4* sa = s_a[q];
+  float2* sb = s_b[q];
+  for (int base = 0; base < wm; base += 64) {
+    const int k = base + lane;
+    bool hit = false;
+    if (k < wm) {
+      // the other waves clear their own bits of this word meanwhile: bit q and the id are this wave's to read
+      const uint32_t e = __hip_atomic_load(pl + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if ((pl_mask(e) >> q) & 1u) {
+        hit = true;
+        const uint32_t g = pl_id(e);
+        const float4 r0 = rec[RECS * (size_t)g + 0], r1 = rec[RECS * (size_t)g + 1];
+        sa[lane] = r0;
+        sb[lane] = make_float2(r1.x, r1.y);
+      }
+    }
+    uint64_t hb = __ballot(hit);
+    const int rel = (int)my_last - base;  // pos = base + j < my_last as j < rel
+    uint64_t live = 0ull;                 // the round's hits some lane blends
+    wave_lds_sync();
+    while (hb) {
+      const int j = (int)__builtin_ctzll(hb);
+      hb = clear_bit(hb, j);
+      const float4 a = sa[j];
+      const float2 b = sb[j];
+      const float dx = a.x - pxf, dy = a.y - pyf;
+      const float power = gpower(a.z, a.w, b.x, dx, dy);
+      const float G = gexp(power);
+      const float alpha = fminf(0.99f, b.y * G);
+      const bool c_last = j < rel, c_pow = !(power > 0.0f), c_alpha = alpha >= 1.0f / 255.0f;
+      if (__builtin_amdgcn_ballot_w64(c_last && c_pow && c_alpha)) live |= 1ull << j;
+    }
+    if (hit && !((live >> lane) & 1ull)) atomicAnd(pl + k, ~(1u << (ID_BITS + q)));
+    wave_lds_sync();
+  }
+}
+
 // The quadrants whose pixels still blend at list position pos (vjp_tile's per-wave bounds) and the entry's
 // effective mask: its quadrant mask restricted to them.  A head entry is one with a non-empty effective mask.
 __device__ __forceinline__ uint32_t eff_mask(uint32_t e, uint32_t pos, const uint32_t* wm4) {
@@ -637,6 +714,11 @@ int launch_lm_rowmap(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, cons
   }
   const unsigned nb = (unsigned)((N + 255) / 256);
   hipLaunchKernelGGL(k_tile_neff, dim3(ntiles), dim3(TILE_PIX), 0, s, v, ib.n_contrib, bb.tile_neff);
+  // the masks refined before the costs and the head flags read them; in the launch order the binning (or an earlier
+  // row map on it) left
+  if (live_masks_on())
+    hipLaunchKernelGGL(k_quad_live, dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges, bb.tile_order, bb.tile_neff,
+                       gb.rec, ib.n_contrib, bb.point_list);
   if (N + 1 >= ntiles) {
     // the LM tile passes' launch order by their modelled cost (hscan holds the costs until k_row_flags rewrites it;
     // only the schedule changes, every tile's results are independent of when it runs)

@@ -211,7 +211,8 @@ __device__ __forceinline__ float gpower(float a, float b, float c, float dx, flo
 }
 
 // point_list entries carry the Gaussian id in the low 28 bits and its quadrant mask (quad_mask,
-// computed once per (tile, Gaussian) pair by k_duplicate) in the top 4 bits.
+// computed once per (tile, Gaussian) pair by k_duplicate) in the top 4 bits; the LM row map clears the bits of the
+// quadrants none of whose pixels blends the entry (k_quad_live, forward.hip).
 constexpr int ID_BITS = 28;
 constexpr uint32_t ID_MASK = (1u << ID_BITS) - 1u;
 constexpr int64_t MAX_P = (int64_t)ID_MASK;  // 268M Gaussians per view and GPU

@@ -86,6 +86,16 @@ class ViewRaster:
             self.active_rows = rows[:n + 1]  # entry j's head rows: [rows[j], rows[j + 1])
         return self._active
 
+    def list_words(self, stream):
+        """(words, slots): copies of the sorted list's raw words (Gaussian id in the low 28 bits, quadrant mask in the
+        top 4) and of the row map's slot of each entry (gslm_inspect_list) -- a diagnostic."""
+        n = max(self.N, 1)
+        words = torch.zeros(n, dtype=torch.int32, device=self.device)
+        slots = torch.zeros(n, dtype=torch.int32, device=self.device)
+        check(lib.gslm_inspect_list(self.binning.data_ptr(), self.binning.numel(), self.N, self.H, self.W,
+                                    words.data_ptr(), slots.data_ptr(), stream), "gslm_inspect_list")
+        return words[:self.N], slots[:self.N]
+
     def active_params(self, model, P, stream):
         """(block, pos): the list-order copy of the parameters the LM chains load per Gaussian (gslm_active_params)
         for active_list(), and the inverse map pos [P] (list row of a Gaussian, -1 off the list).  The block is a
@@ -244,6 +254,7 @@ class LMProblem:
     def evaluate(self):
         """Primal forward of every view; residuals, per-pixel weights and the J^T b seeds from one fused
         epilogue per view (gslm_lm_residual); loss = 2 sum ||r||^2 (device double)."""
+        live_masks()  # (a bad GSLM_LIVE_MASKS is refused before the geometry's row map reads it)
         g = raw_gaussians(self.model)
         loss = torch.zeros((), dtype=torch.float64, device=self.device)
         if self.train_exposure:
@@ -1475,6 +1486,16 @@ def loss_set_group():
     if not 1 <= k <= 8:
         raise ValueError(f"GSLM_LOSS_SET_GROUP={raw!r}: sets per blend pass must be an integer in 1..8")
     return k
+
+
+def live_masks():
+    """Whether the LM row map refines the list's quadrant masks to the visits some pixel blends (GSLM_LIVE_MASKS,
+    default 1; 0 = the binning's own masks, for A/B runs).  The library reads the variable at every row map; any
+    value but "0" and "1" is refused here."""
+    raw = os.environ.get("GSLM_LIVE_MASKS", "1")
+    if raw not in ("0", "1"):
+        raise ValueError(f"GSLM_LIVE_MASKS={raw!r}: 1 (refine the quadrant masks, the default) or 0")
+    return raw == "1"
 
 
 class LossEvaluator:

@@ -282,7 +282,16 @@ int gslm_matvec_view(const gslm_view* view, const gslm_gaussians* g, const gslm_
  * the largest n_contrib of their tile: every later entry's row would be zero), packed per Gaussian; it holds
  * each sorted entry's row slot (in the binning buffer's free sort ping-pong half) and the per-Gaussian row
  * offsets (in the scratch).  It depends on the geometry only, so an LM step's CG loop builds it once; without
- * the flag RENDER rebuilds it. */
+ * the flag RENDER rebuilds it.
+ * Building the row map WRITES the binning workspace (the `const void* binning` of the gslm_matvec_view* forms: their
+ * RENDER stage without the flag, the fused product, the J^T b / pixel_seed pass and the exposure form alike;
+ * gslm_backward and gslm_jvp build no row map and leave the binning as it is): besides the row slots it
+ * clears, in the sorted list's words, the quadrant-mask bits of the (entry, quadrant) visits that no pixel blends
+ * (inside the image, list position below the pixel's n_contrib, !(power > 0), alpha >= 1/255).  The tile passes skip
+ * those visits and compute the same bits; refining a refined list changes nothing; the next forward rebuilds the
+ * list.  The environment variable GSLM_LIVE_MASKS=0 leaves the binning's masks as they are (A/B runs).  The library
+ * reads it at every row map and takes any other value as on; gslm.lm.live_masks() refuses values other than 0 and 1
+ * for the Python host. */
 #define GSLM_MV_TAIL_CLEAN 1
 /* opts->flags: GSLM_MV_SH_REST_PROJECTED -- single-view Krylov space of the SH-rest group.  With one view,
  * Gaussian i's SH-rest columns of J are B_rest(dir_i) (x) d rgb, so J^T W J + D (D a scalar on the group)
@@ -800,6 +809,13 @@ int gslm_inspect(const void* geom, int64_t P, const void* binning, int64_t num_r
  * [hscan[goff[i]], hscan[goff[i] + tiles_touched[i]]).  Either output may be NULL.  Additive, still ABI 9. */
 int gslm_inspect_rowmap(const void* geom, int64_t P, int64_t num_rendered, const void* scratch, size_t scratch_bytes,
                         uint32_t* goff, uint32_t* hscan, void* stream);
+
+/* The sorted list's raw words of a binning, copied device to device: words [num_rendered] u32 (Gaussian id in the low
+ * 28 bits, quadrant mask in the top 4 -- the binning's masks, or those the LM row map refined to the visits some
+ * pixel blends, GSLM_LIVE_MASKS) and slots [num_rendered] u32 (the row map's head-row slot of each sorted entry;
+ * valid as gslm_inspect_rowmap's outputs are).  Either output may be NULL.  Additive, still ABI 9. */
+int gslm_inspect_list(const void* binning, size_t binning_bytes, int64_t num_rendered, int32_t H, int32_t W,
+                      uint32_t* words, uint32_t* slots, void* stream);
 
 /* Device self-test of the wave primitives (one 64-lane wave).  in: [64][8] floats, out: [64].
  * which = 0: transposed 8-value reduction (lane l returns the sum of value (l >> 3) & 7);
