@@ -17,6 +17,8 @@ import numpy as np
 import pytest
 import torch
 
+from preprocess_layouts import _al, _off  # the geometry workspace's 256-B aligned offsets, stated once
+
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
 
@@ -254,15 +256,6 @@ def test_preprocess_views_equals_per_view_preprocess(nviews):
         rect = b[k][r0:r0 + 8 * P].view(torch.int64)
         assert torch.equal(rc[vis][:, 12:14].contiguous().view(torch.int64).reshape(-1), rect[vis])
         assert bool((rc[~vis][:, 12:14] == 0).all())
-
-
-def _al(x):
-    return (x + 255) // 256 * 256
-
-
-def _off(rec, keys):
-    """Byte offset of the tile counts in the geometry layout (rec, depth_key, tiles, ...; 256-B aligned, api.hip)."""
-    return _al(rec) + _al(keys)
 
 
 @pytest.mark.parametrize("P", [1, 5, 63, 65, 129])
