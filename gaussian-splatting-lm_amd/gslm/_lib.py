@@ -526,3 +526,18 @@ def make_grads(means2D=None, means3D=None, opacities=None, scales=None, rotation
 
 def u8(nbytes, device):
     return torch.empty(max(int(nbytes), 1), dtype=torch.uint8, device=device)
+
+
+def view_ptr(views, c0=0):
+    """gslm_view* to entry c0 of a ctypes array of GslmView (the chunked calls over a view batch)."""
+    return ctypes.cast(ctypes.byref(views, c0 * ctypes.sizeof(GslmView)), ctypes.POINTER(GslmView))
+
+
+def extend_opts(opts, cls, flag):
+    """The options `opts` as the base of an extended struct `cls` (GslmMatvecOptsLean, GslmMatvecOptsExposure) with
+    `flag` set in base.flags -- the library reads the extension behind the base when it sees the flag.  The caller
+    fills the extension."""
+    ext = cls()
+    ctypes.memmove(ctypes.addressof(ext.base), ctypes.addressof(opts), ctypes.sizeof(opts))
+    ext.base.flags |= flag
+    return ext

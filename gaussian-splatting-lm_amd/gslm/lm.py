@@ -38,6 +38,17 @@ DEFAULT_DAMP = {"xyz": 5e2, "features_dc": 5e-2, "features_rest": 5e-2, "scaling
                 "opacity": 5e-2, "exposure": 1e1}
 
 
+def _grown(buf, need, device, main=None, side=None):
+    """The workspace `buf` when it holds `need` bytes, else a new one with 25 % + 4096 bytes of slack (a list that
+    grows a little from one geometry to the next is not allocated again).  side: the stream that used the old
+    buffer; it is freed on the stream `main`, which therefore waits for `side` first."""
+    if buf is not None and buf.numel() >= need:
+        return buf
+    if buf is not None and side is not None:
+        main.wait_stream(side)
+    return _lib.u8(int(need * 1.25) + 4096, device)
+
+
 class ViewRaster:
     """Primal forward of one view on raw GaussianModel leaves + the buffers the matvec reuses."""
 
@@ -133,18 +144,13 @@ class ViewRaster:
         n = ctypes.c_int64(0)
         check(lib.gslm_num_rendered(self.geom.data_ptr(), P, ctypes.byref(n), stream), "gslm_num_rendered")
         self.N = int(n.value)
-        need = lib.gslm_binning_bytes(self.N, self.H, self.W)
-        if self.binning is None or self.binning.numel() < need:
-            self.binning = _lib.u8(int(need * 1.25) + 4096, dev)
+        self.binning = _grown(self.binning, lib.gslm_binning_bytes(self.N, self.H, self.W), dev)
         check(lib.gslm_rasterize(ctypes.byref(self.view), P, self.geom.data_ptr(), self.binning.data_ptr(),
                                  self.binning.numel(), self.N, self.image.data_ptr(), self.image.numel(),
                                  self.color.data_ptr(), self.invdepth.data_ptr() if want_invdepth else None, stream),
               "gslm_rasterize")
-        need = lib.gslm_scratch_bytes(P, self.N)
-        if self.scratch is None or self.scratch.numel() < need:
-            self.scratch = _lib.u8(int(need * 1.25) + 4096, dev)
+        self.scratch = _grown(self.scratch, lib.gslm_scratch_bytes(P, self.N), dev)
         return self.color
-
 
     def forward_dev(self, g, stream, want_invdepth=True, n_out=None):
         """forward() without the pair-count read-back between the preprocess and the binning (gslm_rasterize_dev):
@@ -170,8 +176,113 @@ class ViewRaster:
         """List capacity of the binning workspace (forward_dev renders at most this many pairs)."""
         return 0 if self.binning is None else int(lib.gslm_binning_capacity(self.binning.numel(), self.H, self.W))
 
+    def product(self, g, vs, weight, mask_xyz, ys, opts, stream, what, active=None):
+        """gslm_matvec_view_ex on this view's geometry, binning, image and scratch: the stages and flags of `opts`
+        from the input grads struct vs (weight: the per-pixel weights, or the seed / J v image of the stage) into ys.
+        active = (ids, na): vs and ys hold the listed Gaussians only -- gslm_matvec_view_active with this view's
+        rows of the list.  The call alone: tail_clean and the flags are the caller's."""
+        ws = (self.geom.data_ptr(), self.binning.data_ptr(), self.N, self.image.data_ptr(), self.scratch.data_ptr(),
+              self.scratch.numel())
+        if active is not None:
+            ids, na = active
+            check(lib.gslm_matvec_view_active(ctypes.byref(self.view), ctypes.byref(g), ctypes.byref(vs), weight,
+                                              mask_xyz, *ws, ctypes.byref(ys), ctypes.byref(opts),
+                                              ids.data_ptr() if na else None, self.active_rows.data_ptr(), na, stream),
+                  what.replace("_ex", "_active"))
+            return
+        check(lib.gslm_matvec_view_ex(ctypes.byref(self.view), ctypes.byref(g), ctypes.byref(vs), weight, mask_xyz,
+                                      *ws, ctypes.byref(ys), ctypes.byref(opts), stream), what)
 
-class LMProblem:
+
+class _ProductOpts:
+    """The options every operator with a `layout`, `_damps`, `dot_scratch` and `mv_flags` builds around its products
+    (LMProblem and its subclasses; gslm.parallel.GaussianShardedOperator on its shard's layout)."""
+
+    def _opts(self, vr, stages, cg_ctl=None):
+        """gslm_matvec_opts of a product on view vr: the stages, the layout's flag and GSLM_MV_TAIL_CLEAN while the
+        view's scratch holds the row map of an earlier product on its geometry; cg_ctl: see matvec_dot."""
+        opts = _lib.GslmMatvecOpts()
+        opts.stages = stages
+        opts.flags = (MV_TAIL_CLEAN if vr.tail_clean else 0) | self.mv_flags
+        opts.cg_ctl = cg_ctl
+        return opts
+
+    def _dot_opts(self, opts, dot_out):
+        """<v, y> fused into the gather: summed to the device double dot_out, or with None left as the gather's
+        block partials in dot_scratch (the lean loop's dot_defer)."""
+        opts.dot_vy = dot_out
+        opts.dot_scratch = self.dot_scratch.data_ptr()
+        opts.dot_scratch_bytes = self.dot_scratch.numel() * 8
+
+    # pre = (s, beta_num, beta_den[, x, alpha_num, alpha_den]): before the product, [x += alpha v then]
+    # v = s + beta v -- the CG direction update (and the deferred x update) of the previous iteration
+    def _pre_opts(self, opts, v, pre):
+        """Returns the grads struct of s, which opts points to: the caller keeps it alive for the call."""
+        s, num, den = pre[:3]
+        e0, e1 = self.layout.offsets["exposure"]
+        ss = self.layout.grads_struct(s)
+        opts.xpby_s = ctypes.addressof(ss)
+        opts.beta_num, opts.beta_den = num, den
+        if e1 > e0:
+            opts.xpby_tail_v = v.data_ptr() + 4 * e0
+            opts.xpby_tail_s = s.data_ptr() + 4 * e0
+            opts.xpby_tail_n = e1 - e0
+        if len(pre) > 3 and pre[3] is not None:
+            x, anum, aden = pre[3:]
+            opts.alpha_num, opts.alpha_den = anum, aden
+            opts.xpby_x_offset = x.data_ptr() - v.data_ptr()
+        return ss
+
+    def _exposure_tail(self, v, y, damp=True, exposure_zero=False):
+        """The exposure slice of y = [D v +] J^T W J v where J has no exposure column: D v, or zero.
+        exposure_zero: the slices of v and y are zero already (matvec_dot) -- nothing is launched, as for an empty
+        slice."""
+        e0, e1 = self.layout.offsets["exposure"]
+        if exposure_zero or e1 == e0:
+            return
+        if damp:
+            torch.mul(v[e0:e1], float(self._damps[6]), out=y[e0:e1])
+        else:
+            y[e0:e1].zero_()
+
+
+class _StageTimes:
+    """stage_times of an operator whose product records `_mark(k)` between its STAGES."""
+
+    _events = None  # HIP events recorded between the product's stages
+
+    def _mark(self, k):
+        if self._events is not None:
+            self._events[k].record()
+
+    def stage_times(self, v, reps=10):
+        """Per-stage time of a product of direction v (ms, mean over `reps`): HIP events on the product's stream
+        between the stages of STAGES (an exchange's all-to-alls include their wait)."""
+        y = self.zeros()
+        evs = []
+        for _ in range(reps):
+            self._events = [torch.cuda.Event(enable_timing=True) for _ in range(len(self.STAGES) + 1)]
+            self.matvec_dot(v, y, None)
+            evs.append(self._events)
+            self._events = None
+        torch.cuda.synchronize()
+        out = {name: sum(e[k].elapsed_time(e[k + 1]) for e in evs) / reps for k, name in enumerate(self.STAGES)}
+        out["total"] = sum(e[0].elapsed_time(e[-1]) for e in evs) / reps
+        return out
+
+
+def _exposure_index(model, cams):
+    """train_exposure: each camera's row of model._exposure (model.exposure_mapping); ValueError for a model that
+    renders with pretrained exposures or a camera without a row."""
+    if getattr(model, "pretrained_exposures", None) is not None:
+        raise ValueError("train_exposure: the model renders with pretrained exposures, which are not parameters")
+    missing = [c.image_name for c in cams if c.image_name not in model.exposure_mapping]
+    if missing:
+        raise ValueError(f"train_exposure: no row of model._exposure for {missing} (model.exposure_mapping)")
+    return [int(model.exposure_mapping[c.image_name]) for c in cams]
+
+
+class LMProblem(_ProductOpts):
     """The LM normal equations of one camera batch (one LM step's worth of cached geometry)."""
 
     def __init__(self, model, cams, bg, gts=None, alpha_masks=None, mask_xyz=True, damp=None, device="cuda",
@@ -232,15 +343,10 @@ class LMProblem:
     def _init_exposure(self, model, cams, device):
         if self.ssim or not self.mask_xyz:
             raise ValueError("train_exposure runs on the LM rows with the plain residual (mask_xyz=True, ssim=False)")
-        if getattr(model, "pretrained_exposures", None) is not None:
-            raise ValueError("train_exposure: the model renders with pretrained exposures, which are not parameters")
-        missing = [c.image_name for c in cams if c.image_name not in model.exposure_mapping]
-        if missing:
-            raise ValueError(f"train_exposure: no row of model._exposure for {missing} (model.exposure_mapping)")
+        self.exp_idx = _exposure_index(model, cams)
         X = model._exposure
         if X.dtype != torch.float32 or not X.is_contiguous() or X.shape[1:] != (3, 4):
             raise ValueError("train_exposure: model._exposure must be contiguous float32 [n, 3, 4]")
-        self.exp_idx = [int(model.exposure_mapping[c.image_name]) for c in cams]
         self._exp_rhs = torch.zeros(X.numel(), dtype=torch.float32, device=device)  # the exposure rows of J^T b
         self._exp_u = [None] * len(cams)
         self._exp_scratch = torch.empty(lib.gslm_exposure_scratch_bytes(1, 1) // 8, dtype=torch.float64,
@@ -321,14 +427,9 @@ class LMProblem:
         if fused and self.mask_xyz:
             ys = self.layout.grads_struct(out)
             for b, vr in enumerate(self.views):
-                opts = _lib.GslmMatvecOpts()
-                opts.stages = 2 | 4 | (STAGE_OVERWRITE if b == 0 else 0)  # RENDER | GATHER
-                opts.flags = (MV_TAIL_CLEAN if vr.tail_clean else 0) | self.mv_flags
+                opts = self._opts(vr, 2 | 4 | (STAGE_OVERWRITE if b == 0 else 0))  # RENDER | GATHER
                 opts.pixel_seed = self.seeds[b].data_ptr()
-                check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(ys),
-                                              self.seeds[b].data_ptr(), 1, vr.geom.data_ptr(), vr.binning.data_ptr(),
-                                              vr.N, vr.image.data_ptr(), vr.scratch.data_ptr(), vr.scratch.numel(),
-                                              ctypes.byref(ys), ctypes.byref(opts), self.stream), "gslm_matvec_view_ex")
+                vr.product(g, ys, self.seeds[b].data_ptr(), 1, ys, opts, self.stream, "gslm_matvec_view_ex")
                 vr.tail_clean = True
             if not self.views:
                 out.zero_()
@@ -406,8 +507,9 @@ class LMProblem:
             dst[b0:b1].copy_(src[a0:a1])
 
     def expand(self, x, out=None):
-        """A vector of this problem's layout in the reference's (full_layout); x itself when not projected."""
-        if not self.layout.rest_projected:
+        """A vector of this problem's layout in the reference's (full_layout); x itself when the layout carries the
+        SH-rest group whole (neither projected nor in the batch's coordinates)."""
+        if not (self.layout.rest_projected or self.layout.rest_views):
             return x
         out = torch.empty(self.full_layout.numel, dtype=torch.float32, device=x.device) if out is None else out
         self._copy_other_groups(x, out, self.layout, self.full_layout)
@@ -415,8 +517,8 @@ class LMProblem:
         return out
 
     def project(self, x_full, out=None):
-        """full_layout -> this problem's layout (the orthogonal projection onto the view's SH-rest span)."""
-        if not self.layout.rest_projected:
+        """full_layout -> this problem's layout (the orthogonal projection onto the views' SH-rest span)."""
+        if not (self.layout.rest_projected or self.layout.rest_views):
             return x_full if out is None else out.copy_(x_full)
         out = torch.empty(self.layout.numel, dtype=torch.float32, device=x_full.device) if out is None else out
         self._copy_other_groups(x_full, out, self.full_layout, self.layout)
@@ -476,20 +578,13 @@ class LMProblem:
         last = len(self.views) - 1
         e0, e1 = self.layout.offsets["exposure"]
         for b, vr in enumerate(self.views):
-            opts = _lib.GslmMatvecOpts()
-            opts.stages = STAGE_ALL | (STAGE_OVERWRITE if b == 0 else 0)
-            opts.flags = (MV_TAIL_CLEAN if vr.tail_clean else 0) | self.mv_flags
+            opts = self._opts(vr, STAGE_ALL | (STAGE_OVERWRITE if b == 0 else 0), cg_ctl)
             opts.damp7 = self._damps if (damp and b == 0) else None
-            opts.cg_ctl = cg_ctl
             if pre is not None and b == 0:
                 ss = self._pre_opts(opts, v, pre)  # noqa: F841  (kept alive for the call)
-            if dot_out is not None and b == last:
-                opts.dot_vy = dot_out
-                opts.dot_scratch = self.dot_scratch.data_ptr()
-                opts.dot_scratch_bytes = self.dot_scratch.numel() * 8
-            if lean is not None and lean.dot_defer:  # <v, y> stays as the gather's partials in dot_scratch
-                opts.dot_scratch = self.dot_scratch.data_ptr()
-                opts.dot_scratch_bytes = self.dot_scratch.numel() * 8
+            fuse = dot_out is not None and b == last
+            if fuse or (lean is not None and lean.dot_defer):  # (deferred: <v, y> stays as the gather's partials)
+                self._dot_opts(opts, dot_out if fuse else None)
             if self.ssim:
                 self._ssim_product(b, vr, g, vs, ys, opts)
                 continue
@@ -504,20 +599,14 @@ class LMProblem:
             if self._exp_rest is not None:
                 vt, yt = v[e0:e1].view(-1, 12), y[e0:e1].view(-1, 12)
                 yt[self._exp_rest] = vt[self._exp_rest] * (float(self._damps[6]) if damp else 0.0)
-        elif exposure_zero:
-            pass  # y[e0:e1] = D v[e0:e1] = 0 already (matvec_dot)
-        elif damp:
-            torch.mul(v[e0:e1], float(self._damps[6]), out=y[e0:e1])  # J has no exposure column
         else:
-            y[e0:e1].zero_()
+            self._exposure_tail(v, y, damp, exposure_zero)
         return y
 
     def _exposure_opts(self, opts, b, vr, v, y, e0, damp):
         """View b's options extended by its camera's exposure (GSLM_MV_EXPOSURE): X from the model, V and Y the
         camera's 12 floats of v's and y's exposure tail; the camera's first view writes Y and adds D V."""
-        ext = _lib.GslmMatvecOptsExposure()
-        ctypes.memmove(ctypes.addressof(ext.base), ctypes.addressof(opts), ctypes.sizeof(opts))
-        ext.base.flags |= MV_EXPOSURE
+        ext = _lib.extend_opts(opts, _lib.GslmMatvecOptsExposure, MV_EXPOSURE)
         k = self.exp_idx[b]
         x = ext.exposure
         x.exposure = self.model._exposure.data_ptr() + 48 * k
@@ -531,44 +620,12 @@ class LMProblem:
         return ext
 
     def _view_product(self, vr, g, vs, weight, ys, opts, what, lean=None):
-        """gslm_matvec_view_ex on one view -- or, on an active_view() (v and y hold the listed Gaussians only),
-        gslm_matvec_view_active (with the lean loop's options when lean is given)."""
-        if lean is not None:  # the options extended by the lean loop's (GSLM_MV_LEAN)
-            ext = _lib.GslmMatvecOptsLean()
-            ctypes.memmove(ctypes.addressof(ext.base), ctypes.addressof(opts), ctypes.sizeof(opts))
-            ext.base.flags |= MV_LEAN
-            ext.lean = lean
-            opts = ext
-        if self._active is not None:
-            ids, na = self._active
-            check(lib.gslm_matvec_view_active(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(vs), weight,
-                                              int(self.mask_xyz), vr.geom.data_ptr(), vr.binning.data_ptr(), vr.N,
-                                              vr.image.data_ptr(), vr.scratch.data_ptr(), vr.scratch.numel(),
-                                              ctypes.byref(ys), ctypes.byref(opts), ids.data_ptr() if na else None,
-                                              vr.active_rows.data_ptr(), na, self.stream),
-                  what.replace("_ex", "_active"))
-            return
-        check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(vs), weight,
-                                      int(self.mask_xyz), vr.geom.data_ptr(), vr.binning.data_ptr(), vr.N,
-                                      vr.image.data_ptr(), vr.scratch.data_ptr(), vr.scratch.numel(), ctypes.byref(ys),
-                                      ctypes.byref(opts), self.stream), what)
-
-    # pre = (s, beta_num, beta_den[, x, alpha_num, alpha_den]): before the product, [x += alpha v then]
-    # v = s + beta v -- the CG direction update (and the deferred x update) of the previous iteration
-    def _pre_opts(self, opts, v, pre):
-        s, num, den = pre[:3]
-        e0, e1 = self.layout.offsets["exposure"]
-        ss = self.layout.grads_struct(s)
-        opts.xpby_s = ctypes.addressof(ss)
-        opts.beta_num, opts.beta_den = num, den
-        opts.xpby_tail_v = v.data_ptr() + 4 * e0
-        opts.xpby_tail_s = s.data_ptr() + 4 * e0
-        opts.xpby_tail_n = e1 - e0
-        if len(pre) > 3 and pre[3] is not None:
-            x, anum, aden = pre[3:]
-            opts.alpha_num, opts.alpha_den = anum, aden
-            opts.xpby_x_offset = x.data_ptr() - v.data_ptr()
-        return ss
+        """ViewRaster.product of this problem on one view: on an active_view() (v and y hold the listed Gaussians
+        only) the active-list form, with the lean loop's options when lean is given (GSLM_MV_LEAN)."""
+        if lean is not None:
+            opts = _lib.extend_opts(opts, _lib.GslmMatvecOptsLean, MV_LEAN)
+            opts.lean = lean
+        vr.product(g, vs, weight, int(self.mask_xyz), ys, opts, self.stream, what, active=self._active)
 
     def _pre_without_views(self, v, pre):
         s, num, den = pre[:3]
@@ -583,24 +640,18 @@ class LMProblem:
         M (d1^2 + S^T c2^2 S) M (gslm_ssim_normal) -> seeded back-to-front pass + LM gather.
         opts carries this view's gather options (overwrite, damping, dot) and the fused xpby."""
         jv, u = self._jv[b], self._u[b]
-        o1 = _lib.GslmMatvecOpts()
-        o1.stages = 1 | 2  # TANGENT | RENDER
-        o1.flags = (MV_TAIL_CLEAN if vr.tail_clean else 0) | self.mv_flags  # (read by the active-list form only)
+        o1 = self._opts(vr, 1 | 2, opts.cg_ctl)  # TANGENT | RENDER (the flags are read by the active-list form only)
         o1.jv_out = jv.data_ptr()
-        o1.xpby_s, o1.beta_num, o1.beta_den = opts.xpby_s, opts.beta_num, opts.beta_den
-        o1.xpby_tail_v, o1.xpby_tail_s, o1.xpby_tail_n = opts.xpby_tail_v, opts.xpby_tail_s, opts.xpby_tail_n
-        o1.alpha_num, o1.alpha_den, o1.xpby_x_offset = opts.alpha_num, opts.alpha_den, opts.xpby_x_offset
-        o1.cg_ctl = opts.cg_ctl
+        for f in ("xpby_s", "beta_num", "beta_den", "xpby_tail_v", "xpby_tail_s", "xpby_tail_n", "alpha_num",
+                  "alpha_den", "xpby_x_offset"):
+            setattr(o1, f, getattr(opts, f))
         self._view_product(vr, g, vs, jv.data_ptr(), ys, o1, "gslm_matvec_view_ex(jv)")
         check(lib.gslm_ssim_normal(vr.H, vr.W, self.gts[b].data_ptr(), self.ssim_state[b].data_ptr(), jv.data_ptr(),
                                    u.data_ptr(), self.stream), "gslm_ssim_normal")
-        o2 = _lib.GslmMatvecOpts()
-        o2.stages = 2 | 4 | (opts.stages & STAGE_OVERWRITE)  # RENDER | GATHER
-        o2.flags = (MV_TAIL_CLEAN if vr.tail_clean else 0) | self.mv_flags
+        o2 = self._opts(vr, 2 | 4 | (opts.stages & STAGE_OVERWRITE), opts.cg_ctl)  # RENDER | GATHER
         o2.pixel_seed = u.data_ptr()
-        o2.damp7 = opts.damp7
-        o2.dot_vy, o2.dot_scratch, o2.dot_scratch_bytes = opts.dot_vy, opts.dot_scratch, opts.dot_scratch_bytes
-        o2.cg_ctl = opts.cg_ctl
+        for f in ("damp7", "dot_vy", "dot_scratch", "dot_scratch_bytes"):
+            setattr(o2, f, getattr(opts, f))
         self._view_product(vr, g, vs, u.data_ptr(), ys, o2, "gslm_matvec_view_ex(seed)")
         vr.tail_clean = True
 
@@ -627,17 +678,11 @@ class LMProblem:
         if pre is not None and not self.views:
             self._pre_without_views(v, pre)
         for b, vr in enumerate(self.views):
-            opts = _lib.GslmMatvecOpts()
-            opts.stages = 1 | 2 | 16  # TANGENT | RENDER | SCREEN
-            opts.flags = MV_TAIL_CLEAN if vr.tail_clean else 0
+            opts = self._opts(vr, 1 | 2 | 16, cg_ctl)  # TANGENT | RENDER | SCREEN
             opts.screen_out = screen[b].data_ptr()
-            opts.cg_ctl = cg_ctl
             if pre is not None and b == 0:
                 ss = self._pre_opts(opts, v, pre)  # noqa: F841
-            check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(vs),
-                                          self.weights[b].data_ptr(), 1, vr.geom.data_ptr(), vr.binning.data_ptr(),
-                                          vr.N, vr.image.data_ptr(), vr.scratch.data_ptr(), vr.scratch.numel(),
-                                          ctypes.byref(ys), ctypes.byref(opts), self.stream), "gslm_matvec_view_ex")
+            vr.product(g, vs, self.weights[b].data_ptr(), 1, ys, opts, self.stream, "gslm_matvec_view_ex")
             vr.tail_clean = True
 
     def gather_screen(self, views, screen_all, v, y, dot_out=None, chunk=16):
@@ -653,14 +698,11 @@ class LMProblem:
             opts.stages = (STAGE_ALL | STAGE_OVERWRITE) if c0 == 0 else STAGE_ALL
             opts.damp7 = self._damps if c0 == 0 else None
             if dot_out is not None and c1 == n:
-                opts.dot_vy = dot_out
-                opts.dot_scratch = self.dot_scratch.data_ptr()
-                opts.dot_scratch_bytes = self.dot_scratch.numel() * 8
-            vptr = ctypes.cast(ctypes.byref(views, c0 * ctypes.sizeof(_lib.GslmView)), ctypes.POINTER(_lib.GslmView))
-            check(lib.gslm_gather_screen(vptr, c1 - c0, ctypes.byref(g), screen_all[c0].data_ptr(), ctypes.byref(vs),
-                                         ctypes.byref(ys), ctypes.byref(opts), self.stream), "gslm_gather_screen")
-        e0, e1 = self.layout.offsets["exposure"]
-        torch.mul(v[e0:e1], float(self._damps[6]), out=y[e0:e1])  # J has no exposure column
+                self._dot_opts(opts, dot_out)
+            check(lib.gslm_gather_screen(_lib.view_ptr(views, c0), c1 - c0, ctypes.byref(g),
+                                         screen_all[c0].data_ptr(), ctypes.byref(vs), ctypes.byref(ys),
+                                         ctypes.byref(opts), self.stream), "gslm_gather_screen")
+        self._exposure_tail(v, y)
         return y
 
     def damp_add(self, v, y):
@@ -689,10 +731,7 @@ class LMProblem:
             opts.stages = 1 | 2  # TANGENT | RENDER with jv_out: the colour tangent
             opts.flags = self.mv_flags
             opts.jv_out = out[b].data_ptr()
-            check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(vs),
-                                          out[b].data_ptr(), 1, vr.geom.data_ptr(), vr.binning.data_ptr(), vr.N,
-                                          vr.image.data_ptr(), vr.scratch.data_ptr(), vr.scratch.numel(),
-                                          ctypes.byref(vs), ctypes.byref(opts), self.stream), "gslm_matvec_view_ex(jv)")
+            vr.product(g, vs, out[b].data_ptr(), 1, vs, opts, self.stream, "gslm_matvec_view_ex(jv)")
             out[b].mul_(rmasks[b])
         return out
 
@@ -705,14 +744,9 @@ class LMProblem:
         ys = self.layout.grads_struct(out)
         for b, vr in enumerate(self.views):
             seed = (2.0 * rmasks[b]) * r[b]
-            opts = _lib.GslmMatvecOpts()
-            opts.stages = 2 | 4 | (STAGE_OVERWRITE if b == 0 else 0)  # RENDER | GATHER, seeded
-            opts.flags = (MV_TAIL_CLEAN if vr.tail_clean else 0) | self.mv_flags
+            opts = self._opts(vr, 2 | 4 | (STAGE_OVERWRITE if b == 0 else 0))  # RENDER | GATHER, seeded
             opts.pixel_seed = seed.data_ptr()
-            check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(ys), seed.data_ptr(), 1,
-                                          vr.geom.data_ptr(), vr.binning.data_ptr(), vr.N, vr.image.data_ptr(),
-                                          vr.scratch.data_ptr(), vr.scratch.numel(), ctypes.byref(ys),
-                                          ctypes.byref(opts), self.stream), "gslm_matvec_view_ex(seed)")
+            vr.product(g, ys, seed.data_ptr(), 1, ys, opts, self.stream, "gslm_matvec_view_ex(seed)")
             vr.tail_clean = True
         if not self.views:
             out.zero_()
@@ -738,10 +772,17 @@ class LMProblem:
         ids, na = vr.active_list(self.layout.P, self.stream)
         if na == 0:
             return None  # (every vector of the solve is the exposure tail alone: nothing to save)
+        return self._restricted(ids, na)
+
+    def _restricted(self, ids, na):
+        """The shallow copy of this problem whose vectors hold the na listed Gaussians only: the same layout kind
+        over na rows, the damping arrays at its offsets."""
         act = copy.copy(self)
         act._active = (ids, na)
         act._full = self
-        act.layout = ParamLayout(na, self.layout.K, self.layout.n_exposure, rest_projected=self.layout.rest_projected)
+        lay = self.layout
+        act.layout = ParamLayout(na, lay.K, lay.n_exposure, rest_projected=lay.rest_projected,
+                                 rest_views=lay.rest_views)
         act._bounds, act._damps = act.layout.group_damp_arrays(self.damp)
         return act
 
@@ -796,7 +837,7 @@ class LMProblem:
         return torch.zeros(self.layout.numel, dtype=torch.float32, device=self.device)
 
 
-class BatchedLMProblem(LMProblem):
+class BatchedLMProblem(LMProblem, _StageTimes):
     """LMProblem over several views with one batched pass per product and per J^T b on one GPU (the reference's
     view batch, train_jvp.py --num_images): where LMProblem runs the whole fused product once per view -- the
     per-Gaussian tangent kernel over all P, and a gather that re-reads and re-writes all of y, V times -- this runs
@@ -810,8 +851,7 @@ class BatchedLMProblem(LMProblem):
     mask_xyz=True and the disable_ssim residual only."""
 
     CHUNK = 16  # views per gslm_tangent_views / gslm_gather_views call
-    STAGES = ("tangent_views", "tile_passes", "gather_views")
-    _events = None  # stage_times: HIP events recorded between the product's stages
+    STAGES = ("tangent_views", "tile_passes", "gather_views")  # (_StageTimes.stage_times)
 
     def __init__(self, model, cams, bg, gts=None, alpha_masks=None, mask_xyz=True, damp=None, device="cuda",
                  ssim=False, lambda_dssim=0.2, sh_projection=False, union_active=False):
@@ -881,36 +921,9 @@ class BatchedLMProblem(LMProblem):
         ids, na, hrow, aflags = self.union_list()
         if na == 0:
             return None  # (every vector of the solve is the exposure tail alone: nothing to save)
-        act = copy.copy(self)
-        act._active = (ids, na)
+        act = self._restricted(ids, na)
         act._union_bufs = (hrow, aflags)
-        act._full = self
-        act.layout = ParamLayout(na, self.layout.K, self.layout.n_exposure, rest_views=self.rest_views)
-        act._bounds, act._damps = act.layout.group_damp_arrays(self.damp)
         return act
-
-    def _mark(self, k):
-        if self._events is not None:
-            self._events[k].record()
-
-    def stage_times(self, v, reps=10):
-        """Per-stage time of a product of direction v (ms, mean over `reps`): HIP events on the product's stream
-        between its three stages (as GaussianShardedOperator.stage_times)."""
-        y = self.zeros()
-        evs = []
-        for _ in range(reps):
-            self._events = [torch.cuda.Event(enable_timing=True) for _ in range(len(self.STAGES) + 1)]
-            self.matvec_dot(v, y, None)
-            evs.append(self._events)
-            self._events = None
-        torch.cuda.synchronize()
-        out = {name: sum(e[k].elapsed_time(e[k + 1]) for e in evs) / reps for k, name in enumerate(self.STAGES)}
-        out["total"] = sum(e[0].elapsed_time(e[-1]) for e in evs) / reps
-        return out
-
-    def _view_ptr(self, c0):
-        return ctypes.cast(ctypes.byref(self._views_arr, c0 * ctypes.sizeof(_lib.GslmView)),
-                           ctypes.POINTER(_lib.GslmView))
 
     def evaluate(self):
         """LMProblem.evaluate (the same forwards and residual epilogues: the same loss bits); then, once per geometry,
@@ -953,24 +966,6 @@ class BatchedLMProblem(LMProblem):
                                    mode, src.data_ptr() + 4 * a0, 3 * src_layout.rest_rows, dst.data_ptr() + 4 * b0,
                                    3 * dst_layout.rest_rows, self.stream), "gslm_rest_coords")
 
-    def expand(self, x, out=None):
-        """A vector of this problem's layout in the reference's (full_layout); x itself in the full layout."""
-        if not self.rest_views:
-            return x
-        out = torch.empty(self.full_layout.numel, dtype=torch.float32, device=x.device) if out is None else out
-        self._copy_other_groups(x, out, self.layout, self.full_layout)
-        self._rest_convert(0, x, out, self.layout, self.full_layout)
-        return out
-
-    def project(self, x_full, out=None):
-        """full_layout -> this problem's layout (the orthogonal projection onto the views' SH-rest span)."""
-        if not self.rest_views:
-            return x_full if out is None else out.copy_(x_full)
-        out = torch.empty(self.layout.numel, dtype=torch.float32, device=x_full.device) if out is None else out
-        self._copy_other_groups(x_full, out, self.full_layout, self.layout)
-        self._rest_convert(1, x_full, out, self.full_layout, self.layout)
-        return out
-
     # -------------------------------------------------------------- the batched passes
     def _gather(self, g, vs, ys, damp, dot_out, cg_ctl):
         """gslm_gather_views over the views' head rows: y = [D v +] sum_b C_b^T rows_b, <v, y> with the last chunk."""
@@ -985,20 +980,18 @@ class BatchedLMProblem(LMProblem):
             if R is not None:
                 opts.rest_basis, opts.rest_views, opts.view_base = R.data_ptr(), self.rest_views, c0
             if dot_out is not None and c1 == V:
-                opts.dot_vy = dot_out
-                opts.dot_scratch = self.dot_scratch.data_ptr()
-                opts.dot_scratch_bytes = self.dot_scratch.numel() * 8
-            ws = self._view_ws(c0, c1)
+                self._dot_opts(opts, dot_out)
+            vptr, ws = _lib.view_ptr(self._views_arr, c0), self._view_ws(c0, c1)
             if self._active is not None:  # v and y hold the union list's Gaussians only
                 (ids, na), (hrow, aflags) = self._active, self._union_bufs
                 P = self._full.full_layout.P
-                check(lib.gslm_gather_views_active(self._view_ptr(c0), ws, c1 - c0, ctypes.byref(g), ctypes.byref(vs),
+                check(lib.gslm_gather_views_active(vptr, ws, c1 - c0, ctypes.byref(g), ctypes.byref(vs),
                                                    ctypes.byref(ys), ids.data_ptr(), na,
                                                    hrow.data_ptr() + 4 * c0 * (P + 1), P + 1,
                                                    aflags.data_ptr() + 4 * c0 * P, P, ctypes.byref(opts), self.stream),
                       "gslm_gather_views_active")
                 continue
-            check(lib.gslm_gather_views(self._view_ptr(c0), ws, c1 - c0, ctypes.byref(g), ctypes.byref(vs),
+            check(lib.gslm_gather_views(vptr, ws, c1 - c0, ctypes.byref(g), ctypes.byref(vs),
                                         ctypes.byref(ys), ctypes.byref(opts), self.stream), "gslm_gather_views")
 
     def rhs(self, out, fused=True):
@@ -1007,15 +1000,9 @@ class BatchedLMProblem(LMProblem):
         g = raw_gaussians(self.model)
         ys = self.layout.grads_struct(out)
         for b, vr in enumerate(self.views):
-            opts = _lib.GslmMatvecOpts()
-            opts.stages = 2  # RENDER, seeded
-            opts.flags = MV_TAIL_CLEAN if vr.tail_clean else 0
+            opts = self._opts(vr, 2)  # RENDER, seeded
             opts.pixel_seed = self.seeds[b].data_ptr()
-            check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(ys),
-                                          self.seeds[b].data_ptr(), 1, vr.geom.data_ptr(), vr.binning.data_ptr(),
-                                          vr.N, vr.image.data_ptr(), vr.scratch.data_ptr(), vr.scratch.numel(),
-                                          ctypes.byref(ys), ctypes.byref(opts), self.stream),
-                  "gslm_matvec_view_ex(seed)")
+            vr.product(g, ys, self.seeds[b].data_ptr(), 1, ys, opts, self.stream, "gslm_matvec_view_ex(seed)")
             vr.tail_clean = True
         self._gather(g, ys, ys, False, None, None)
         e0, e1 = self.layout.offsets["exposure"]
@@ -1048,15 +1035,16 @@ class BatchedLMProblem(LMProblem):
                     keep.append(self._pre_opts(opts, v, pre))
                 if R is not None:
                     opts.rest_basis, opts.rest_views, opts.view_base = R.data_ptr(), self.rest_views, c0
+            vptr = _lib.view_ptr(self._views_arr, c0)
             if self._active is not None:  # v (and s, x of pre) hold the union list's Gaussians only
                 (ids, na), aflags = self._active, self._union_bufs[1]
-                check(lib.gslm_tangent_views_active(self._view_ptr(c0), c1 - c0, ctypes.byref(g), ctypes.byref(vs), 1,
+                check(lib.gslm_tangent_views_active(vptr, c1 - c0, ctypes.byref(g), ctypes.byref(vs), 1,
                                                     ids.data_ptr(), na, aflags.data_ptr() + 4 * c0 * P, P,
                                                     self._trec.data_ptr() + 32 * c0 * P, P,
                                                     None if opts is None else ctypes.byref(opts), self.stream),
                       "gslm_tangent_views_active")
                 continue
-            check(lib.gslm_tangent_views(self._view_ptr(c0), c1 - c0, ctypes.byref(g), ctypes.byref(vs), 1,
+            check(lib.gslm_tangent_views(vptr, c1 - c0, ctypes.byref(g), ctypes.byref(vs), 1,
                                          self._flags.data_ptr() + 4 * c0 * P, P,
                                          self._trec.data_ptr() + 32 * c0 * P, P,
                                          None if opts is None else ctypes.byref(opts), self.stream),
@@ -1064,27 +1052,15 @@ class BatchedLMProblem(LMProblem):
         self._mark(1)
         # 2. each view's tile pass from its slice of the table, into its own head rows
         for b, vr in enumerate(self.views):
-            opts = _lib.GslmMatvecOpts()
-            opts.stages = 2  # RENDER
-            opts.flags = MV_TAIL_CLEAN if vr.tail_clean else 0
+            opts = self._opts(vr, 2, cg_ctl)  # RENDER
             opts.trec_in = self._trec[b].data_ptr()
-            opts.cg_ctl = cg_ctl
-            check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(vs),
-                                          self.weights[b].data_ptr(), 1, vr.geom.data_ptr(), vr.binning.data_ptr(),
-                                          vr.N, vr.image.data_ptr(), vr.scratch.data_ptr(), vr.scratch.numel(),
-                                          ctypes.byref(vs), ctypes.byref(opts), self.stream), "gslm_matvec_view_ex")
+            vr.product(g, vs, self.weights[b].data_ptr(), 1, vs, opts, self.stream, "gslm_matvec_view_ex")
             vr.tail_clean = True
         self._mark(2)
         # 3. every view's row sums and chain per Gaussian, y written once per chunk
         self._gather(g, vs, ys, damp, dot_out, cg_ctl)
         self._mark(3)
-        e0, e1 = self.layout.offsets["exposure"]
-        if exposure_zero:
-            pass  # y[e0:e1] = D v[e0:e1] = 0 already (LMProblem.matvec_dot)
-        elif damp:
-            torch.mul(v[e0:e1], float(self._damps[6]), out=y[e0:e1])  # J has no exposure column
-        else:
-            y[e0:e1].zero_()
+        self._exposure_tail(v, y, damp, exposure_zero)
         return y
 
 
@@ -1539,12 +1515,7 @@ class LossEvaluator:
         if self.fused_exposure and device_count:
             raise ValueError("fused_exposure=True: the device-count blend has no exposure form (device_count=False)")
         if self.train_exposure:
-            if getattr(model, "pretrained_exposures", None) is not None:
-                raise ValueError("train_exposure: the model renders with pretrained exposures, which are not parameters")
-            missing = [c.image_name for c in cams if c.image_name not in model.exposure_mapping]
-            if missing:
-                raise ValueError(f"train_exposure: no row of model._exposure for {missing} (model.exposure_mapping)")
-            self.exp_idx = [int(model.exposure_mapping[c.image_name]) for c in cams]
+            self.exp_idx = _exposure_index(model, cams)
         if self.train_exposure and not self.fused_exposure:
             self._exp_scratch = torch.empty(lib.gslm_exposure_scratch_bytes(1, 1) // 8, dtype=torch.float64,
                                             device=device)
@@ -1610,11 +1581,39 @@ class LossEvaluator:
                              f"{self.device}")
         return X.data_ptr()
 
+    def _mask_ptr(self, i):
+        m = self.masks[i]
+        return None if m is None else m.data_ptr()
+
+    def _refresh_orders(self, xyz, P):
+        """Drop the cached depth orders (and their inverses) when xyz moved: another tensor, version or size."""
+        key = (xyz.data_ptr(), xyz._version, P)
+        if key != self._order_key:
+            V = len(self.views)
+            self._order_key, self._orders = key, [None] * V
+            self._pos = [None] * V
+
+    def _preprocess_ordered(self, i, g, geom, sh):
+        """gslm_preprocess_ordered of view i into the geometry workspace `geom` on stream sh: in the view's cached
+        depth order (mode 2), or without one sorting and keeping the order (mode 1)."""
+        mode = 2 if self._orders[i] is not None else 1
+        if mode == 1:
+            self._orders[i] = torch.empty(max(g.P, 1), dtype=torch.int32, device=self.device)
+        check(lib.gslm_preprocess_ordered(ctypes.byref(self.views[i]), ctypes.byref(g), geom.data_ptr(), geom.numel(),
+                                          None, self._orders[i].data_ptr(), mode, sh), "gslm_preprocess_ordered")
+
+    def _total(self, losses):
+        """The views' losses summed in view order (and over the ranks with `reduce`): a device double."""
+        V = len(self.views)
+        loss = losses[:V].sum() if V else losses[0]
+        if self.reduce is not None:
+            self.reduce(loss)
+        return loss
+
     def _blend_loss(self, vw, P, sl, N, i, xrows, scr, out, sh):
         """gslm_rasterize_loss of view i from slot sl into the double at `out`; xrows (fused_exposure): the data
         pointer of the exposure rows, the blend then gslm_rasterize_loss_exposure with the camera's row."""
-        m = self.masks[i]
-        mp = None if m is None else m.data_ptr()
+        mp = self._mask_ptr(i)
         if xrows is None:
             check(lib.gslm_rasterize_loss(ctypes.byref(vw), P, sl["geom"].data_ptr(), sl["binning"].data_ptr(),
                                           sl["binning"].numel(), N, self.gts[i].data_ptr(), mp, scr.data_ptr(),
@@ -1631,15 +1630,12 @@ class LossEvaluator:
         sl = self._slot(0, P)
         vw = self.views[i]
         main_h = torch.cuda.current_stream(self.device).cuda_stream
-        check(lib.gslm_preprocess_ordered(ctypes.byref(vw), ctypes.byref(g), sl["geom"].data_ptr(), sl["geom"].numel(),
-                                          None, self._orders[i].data_ptr(), 2, main_h), "gslm_preprocess_ordered")
+        self._preprocess_ordered(i, g, sl["geom"], main_h)  # (the order is the device-count render's)
         n = ctypes.c_int64(0)
         check(lib.gslm_num_rendered(sl["geom"].data_ptr(), P, ctypes.byref(n), main_h), "gslm_num_rendered")
         N = int(n.value)
         self.num_rendered[i] = N
-        need = lib.gslm_binning_bytes(N, vw.image_height, vw.image_width)
-        if sl["binning"] is None or sl["binning"].numel() < need:
-            sl["binning"] = _lib.u8(int(need * 1.25) + 4096, self.device)
+        sl["binning"] = _grown(sl["binning"], lib.gslm_binning_bytes(N, vw.image_height, vw.image_width), self.device)
         self._blend_loss(vw, P, sl, N, i, None, self.loss_scratch[0], losses.data_ptr() + 8 * i, main_h)
 
     def evaluate(self):
@@ -1654,11 +1650,7 @@ class LossEvaluator:
         losses = torch.zeros(max(V, 1), dtype=torch.float64, device=self.device)
         main = torch.cuda.current_stream(self.device)
         main_h = main.cuda_stream
-        xyz = self.model._xyz
-        key = (xyz.data_ptr(), xyz._version, P)
-        if key != self._order_key:  # xyz moved: sort again
-            self._order_key, self._orders = key, [None] * V
-            self._pos = [None] * V
+        self._refresh_orders(self.model._xyz, P)  # xyz moved: sort again
         # device-count renders' pair counts: allocated and zeroed on the main stream BEFORE the side streams wait on
         # it, so no stream's k_ranges count write can precede the zero fill
         counts = torch.zeros(max(V, 1), dtype=torch.int32, device=self.device)
@@ -1673,31 +1665,18 @@ class LossEvaluator:
                 # device-count renders: per view preprocess -> binning + blend + loss on its stream, no read-back
                 for k, (sl, i) in enumerate(zip(slots, idx)):
                     vw = self.views[i]
-                    mode = 2 if self._orders[i] is not None else 1
-                    if mode == 1:
-                        self._orders[i] = torch.empty(max(P, 1), dtype=torch.int32, device=self.device)
                     _, sh = self._stream(k)
-                    check(lib.gslm_preprocess_ordered(ctypes.byref(vw), ctypes.byref(g), sl["geom"].data_ptr(),
-                                                      sl["geom"].numel(), None, self._orders[i].data_ptr(), mode, sh),
-                          "gslm_preprocess_ordered")
+                    self._preprocess_ordered(i, g, sl["geom"], sh)
                     caps[i] = (k, int(lib.gslm_binning_capacity(sl["binning"].numel(), vw.image_height,
                                                                    vw.image_width)))
-                    m = self.masks[i]
                     scr = self.loss_scratch[k % len(self.streams)]
                     check(lib.gslm_rasterize_loss_dev(ctypes.byref(vw), P, sl["geom"].data_ptr(), sl["binning"].data_ptr(),
-                                                      sl["binning"].numel(), self.gts[i].data_ptr(),
-                                                      None if m is None else m.data_ptr(), scr.data_ptr(),
-                                                      scr.numel() * 8, losses.data_ptr() + 8 * i, 0,
+                                                      sl["binning"].numel(), self.gts[i].data_ptr(), self._mask_ptr(i),
+                                                      scr.data_ptr(), scr.numel() * 8, losses.data_ptr() + 8 * i, 0,
                                                       counts.data_ptr() + 4 * i, sh), "gslm_rasterize_loss_dev")
                 continue
             for k, (sl, i) in enumerate(zip(slots, idx)):
-                mode = 2 if self._orders[i] is not None else 1
-                if mode == 1:
-                    self._orders[i] = torch.empty(max(P, 1), dtype=torch.int32, device=self.device)
-                _, sh = self._stream(k)
-                check(lib.gslm_preprocess_ordered(ctypes.byref(self.views[i]), ctypes.byref(g), sl["geom"].data_ptr(),
-                                                  sl["geom"].numel(), None, self._orders[i].data_ptr(), mode, sh),
-                      "gslm_preprocess_ordered")
+                self._preprocess_ordered(i, g, sl["geom"], self._stream(k)[1])
             for st in self.streams:
                 if st is not None:
                     main.wait_stream(st)
@@ -1710,11 +1689,8 @@ class LossEvaluator:
                 H, W, N = vw.image_height, vw.image_width, int(Ns[k])
                 self.num_rendered[i] = N
                 st, sh = self._stream(k)
-                need = lib.gslm_binning_bytes(N, H, W)
-                if sl["binning"] is None or sl["binning"].numel() < need:
-                    if sl["binning"] is not None and st is not None:
-                        main.wait_stream(st)  # the old buffer is freed on the main stream: after its last use
-                    sl["binning"] = _lib.u8(int(need * 1.25) + 4096, self.device)
+                # (an old buffer is freed on the main stream: after its last use on the view's)
+                sl["binning"] = _grown(sl["binning"], lib.gslm_binning_bytes(N, H, W), self.device, main, st)
                 self._blend_loss(vw, P, sl, N, i, xrows, self.loss_scratch[k % len(self.streams)],
                                  losses.data_ptr() + 8 * i, sh)
         for st in self.streams:
@@ -1729,12 +1705,9 @@ class LossEvaluator:
                     self._render_exact(g, i, losses)
                     vw = self.views[i]
                     need = lib.gslm_binning_bytes(ns[i], vw.image_height, vw.image_width)
-                    if self.slots[k]["binning"].numel() < need:  # and its slot's list grown for the next evaluation
-                        self.slots[k]["binning"] = _lib.u8(int(need * 1.25) + 4096, self.device)
-        loss = losses[:V].sum() if V else losses[0]
-        if self.reduce is not None:
-            self.reduce(loss)
-        return loss
+                    # and its slot's list grown for the next evaluation
+                    self.slots[k]["binning"] = _grown(self.slots[k]["binning"], need, self.device)
+        return self._total(losses)
 
     def _evaluate_exposure(self):
         """evaluate() with train_exposure: per view the forward, then the exposure residual's loss alone."""
@@ -1753,15 +1726,11 @@ class LossEvaluator:
             vr.view = vw
             R = vr.forward(g, stream, want_invdepth=False)
             self.num_rendered[i] = vr.N
-            m = self.masks[i]
             check(lib.gslm_lm_residual_exposure(
-                vr.H, vr.W, R.data_ptr(), self.gts[i].data_ptr(), None if m is None else m.data_ptr(),
+                vr.H, vr.W, R.data_ptr(), self.gts[i].data_ptr(), self._mask_ptr(i),
                 X.data_ptr() + 48 * self.exp_idx[i], None, None, None, None, self._exp_scratch.data_ptr(),
                 self._exp_scratch.numel() * 8, losses.data_ptr() + 8 * i, 0, stream), "gslm_lm_residual_exposure")
-        loss = losses[:V].sum() if V else losses[0]
-        if self.reduce is not None:
-            self.reduce(loss)
-        return loss
+        return self._total(losses)
 
     # ---- the line search's six points with one binning per view (include/gslm.h "shared binning", ABI 8) ----
     def _sets_scratch(self, k, n, H, W):
@@ -1834,10 +1803,7 @@ class LossEvaluator:
         V = len(self.views)
         main = torch.cuda.current_stream(self.device)
         main_h = main.cuda_stream
-        key = (xyz.data_ptr(), xyz._version, P)
-        if key != self._order_key:
-            self._order_key, self._orders = key, [None] * V
-            self._pos = [None] * V
+        self._refresh_orders(xyz, P)
         losses = [torch.zeros(max(V, 1), dtype=torch.float64, device=self.device) for _ in range(n)]
         self.union_counts = [0] * V
         side = [st for st in self.streams if st is not None]
@@ -1852,11 +1818,7 @@ class LossEvaluator:
             # 1. each view's depth order (sorted once while xyz is unchanged) and its inverse, the depth positions
             for k, i in enumerate(idx):
                 if self._orders[i] is None:  # the depth sort (set 0's geometry; only the order is kept)
-                    self._orders[i] = torch.empty(max(P, 1), dtype=torch.int32, device=self.device)
-                    sg = self._sort_geom(P)
-                    check(lib.gslm_preprocess_ordered(ctypes.byref(self.views[i]), ctypes.byref(gs[0]),
-                                                      sg.data_ptr(), sg.numel(), None, self._orders[i].data_ptr(), 1,
-                                                      main_h), "gslm_preprocess_ordered")
+                    self._preprocess_ordered(i, gs[0], self._sort_geom(P), main_h)
                     self._pos[i] = None
                 if self._pos[i] is None:
                     self._pos[i] = torch.empty(max(P, 1), dtype=torch.int32, device=self.device)
@@ -1890,19 +1852,14 @@ class LossEvaluator:
                 H, W, N = vw.image_height, vw.image_width, int(Ns[k])
                 self.union_counts[i] = N
                 st, sh = self._stream(k)
-                need = lib.gslm_union_binning_bytes(N, H, W)
-                bins = self.ubins
-                if bins[k] is None or bins[k].numel() < need:
-                    if bins[k] is not None and st is not None:
-                        main.wait_stream(st)  # freed on the main stream: after its last use
-                    bins[k] = _lib.u8(int(need * 1.25) + 4096, self.device)
-                binning = bins[k]
-                ge = (ctypes.c_void_p * n)(*[sl["geoms"][a].data_ptr() for a in range(n)])
+                # (an old list is freed on the main stream: after its last use on the view's)
+                binning = self.ubins[k] = _grown(self.ubins[k], lib.gslm_union_binning_bytes(N, H, W), self.device,
+                                                 main, st)
+                ge =(ctypes.c_void_p * n)(*[sl["geoms"][a].data_ptr() for a in range(n)])
                 sb = sl["geoms"][0].numel()
                 check(lib.gslm_union_binning(ctypes.byref(vw), P, sl["ugeom"].data_ptr(), binning.data_ptr(),
                                              binning.numel(), N, ge, n, sb, sh), "gslm_union_binning")
-                m = self.masks[i]
-                mp = None if m is None else m.data_ptr()
+                mp = self._mask_ptr(i)
                 xoff = 48 * self.exp_idx[i] if xs is not None else 0
                 if self.loss_sets > 1:  # groups of loss_sets sets, one pass over the union list each
                     gsz = min(self.loss_sets, n)
@@ -1919,9 +1876,9 @@ class LossEvaluator:
                                 "gslm_rasterize_loss_sets_exposure")
                             continue
                         check(lib.gslm_rasterize_loss_sets(ctypes.byref(vw), P, gg, na, a0, sb, binning.data_ptr(),
-                                                           binning.numel(), N, self.gts[i].data_ptr(),
-                                                           None if m is None else m.data_ptr(), scr.data_ptr(),
-                                                           scr.numel() * 8, lp, 0, sh), "gslm_rasterize_loss_sets")
+                                                           binning.numel(), N, self.gts[i].data_ptr(), mp,
+                                                           scr.data_ptr(), scr.numel() * 8, lp, 0, sh),
+                              "gslm_rasterize_loss_sets")
                     continue
                 scr = self.loss_scratch[k % len(self.streams)]
                 for a in range(n):
@@ -1933,9 +1890,8 @@ class LossEvaluator:
                         continue
                     check(lib.gslm_rasterize_loss_slot(ctypes.byref(vw), P, sl["geoms"][a].data_ptr(), sb,
                                                        binning.data_ptr(), binning.numel(), N, a, n, self.gts[i].data_ptr(),
-                                                       None if m is None else m.data_ptr(), scr.data_ptr(),
-                                                       scr.numel() * 8, losses[a].data_ptr() + 8 * i, 0, sh),
-                          "gslm_rasterize_loss_slot")
+                                                       mp, scr.data_ptr(), scr.numel() * 8,
+                                                       losses[a].data_ptr() + 8 * i, 0, sh), "gslm_rasterize_loss_slot")
             if side:
                 evs = []
                 for st in side:
@@ -1945,13 +1901,7 @@ class LossEvaluator:
                 done[par] = evs
         for st in side:
             main.wait_stream(st)
-        out = []
-        for a in range(n):
-            loss = losses[a][:V].sum() if V else losses[a][0]
-            if self.reduce is not None:
-                self.reduce(loss)
-            out.append(loss)
-        return out
+        return [self._total(losses[a]) for a in range(n)]
 
 
 _LS_GROUPS = ("_features_dc", "_features_rest", "_scaling", "_rotation", "_opacity")

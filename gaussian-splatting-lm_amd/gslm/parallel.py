@@ -26,6 +26,7 @@ import os
 import torch
 import torch.distributed as dist
 
+from gslm.lm import _ProductOpts, _StageTimes
 from gslm.params import GROUPS, ParamLayout
 
 
@@ -256,7 +257,7 @@ def _slice_gaussians(g, lo, hi):
     return out
 
 
-class GaussianShardedOperator:
+class GaussianShardedOperator(_ProductOpts, _StageTimes):
     """The Gaussian-sharded exchange (exchange "gaussian").
 
     Views stay sharded as in ShardedOperator (rank r renders its block of `per` views), and in addition
@@ -326,7 +327,6 @@ class GaussianShardedOperator:
             self._bufs = None
         if hasattr(local, "_damps"):
             self._damps = local._damps
-        self._events = None  # stage_times: HIP events recorded between the product's stages
 
     def __getattr__(self, name):  # stream, dot_scratch, views, weights, model, ...
         return getattr(self.local, name)
@@ -396,8 +396,7 @@ class GaussianShardedOperator:
         from gslm import _lib
         from gslm.params import raw_gaussians
         gs = _slice_gaussians(raw_gaussians(self.local.model), self.lo, self.hi)
-        vptr = ctypes.cast(ctypes.byref(self.views_kt, 0), ctypes.POINTER(_lib.GslmView))
-        return gs, vptr
+        return gs, _lib.view_ptr(self.views_kt)
 
     def rest_basis(self):
         """gslm_rest_basis of this shard's Gaussians over the job's views (recomputed per geometry)."""
@@ -561,42 +560,8 @@ class GaussianShardedOperator:
         for k in range(self.per):
             self._all_to_all(b["flags"][k], b["flags_local"][k])
 
-    def _pre_opts(self, opts, v, pre):
-        s, num, den = pre[:3]
-        ss = self.layout.grads_struct(s)
-        opts.xpby_s = ctypes.addressof(ss)
-        opts.beta_num, opts.beta_den = num, den
-        e0, e1 = self.layout.offsets["exposure"]
-        if e1 > e0:
-            opts.xpby_tail_v = v.data_ptr() + 4 * e0
-            opts.xpby_tail_s = s.data_ptr() + 4 * e0
-            opts.xpby_tail_n = e1 - e0
-        if len(pre) > 3 and pre[3] is not None:
-            x, anum, aden = pre[3:]
-            opts.alpha_num, opts.alpha_den = anum, aden
-            opts.xpby_x_offset = x.data_ptr() - v.data_ptr()
-        return ss
-
+    # the five stages of _matvec_kernels (_StageTimes.stage_times)
     STAGES = ("tangent_views", "all_to_all_trec", "render_screen", "all_to_all_screen", "gather_screen")
-
-    def stage_times(self, v, reps=10):
-        """Per-stage time of this rank's product (ms, mean over `reps` products of direction v): HIP events on the
-        product's stream between the five stages of _matvec_kernels (the all-to-alls include their wait)."""
-        y = self.zeros()
-        evs = []
-        for _ in range(reps):
-            self._events = [torch.cuda.Event(enable_timing=True) for _ in range(len(self.STAGES) + 1)]
-            self.matvec_dot(v, y, None)
-            evs.append(self._events)
-            self._events = None
-        torch.cuda.synchronize()
-        out = {name: sum(e[k].elapsed_time(e[k + 1]) for e in evs) / reps for k, name in enumerate(self.STAGES)}
-        out["total"] = sum(e[0].elapsed_time(e[-1]) for e in evs) / reps
-        return out
-
-    def _mark(self, k):
-        if self._events is not None:
-            self._events[k].record()
 
     def _matvec_kernels(self, v, y, dot_out, pre, cg_ctl=None):
         from gslm import _lib
@@ -612,7 +577,6 @@ class GaussianShardedOperator:
         gs = _slice_gaussians(g, self.lo, self.hi)
         vs = self.layout.grads_struct(v)
         ys = self.layout.grads_struct(y)
-        vsz = ctypes.sizeof(_lib.GslmView)
         keep = []
         if pre is not None and self.hi == self.lo:
             # empty shard: the direction update has nothing here but rank 0's exposure tail, which an empty
@@ -639,7 +603,7 @@ class GaussianShardedOperator:
                 keep.append(self._pre_opts(opts, v, pre))
             if R is not None:
                 opts.rest_basis, opts.rest_views, opts.view_base = R.data_ptr(), self.rest_views, c0
-            vptr = ctypes.cast(ctypes.byref(self.views_kt, c0 * vsz), ctypes.POINTER(_lib.GslmView))
+            vptr = _lib.view_ptr(self.views_kt, c0)
             check(lib.gslm_tangent_views(vptr, c1 - c0, ctypes.byref(gs), ctypes.byref(vs), int(self.mask_xyz),
                                          b["flags"].data_ptr() + 4 * c0 * S, S,
                                          b["trec_send"].data_ptr() + 32 * c0 * S, S,
@@ -659,16 +623,10 @@ class GaussianShardedOperator:
         for k, vr in enumerate(loc.views):
             if overlap and works[k] is not None:
                 works[k].wait()  # the compute stream waits for view k's table only
-            opts = _lib.GslmMatvecOpts()
-            opts.stages = 2 | 16  # RENDER | SCREEN
-            opts.flags = 1 if vr.tail_clean else 0  # GSLM_MV_TAIL_CLEAN
+            opts = self._opts(vr, 2 | 16, cg_ctl)  # RENDER | SCREEN
             opts.screen_out = b["screen_send"][k].data_ptr()
             opts.trec_in = b["trec_recv"][k].data_ptr()
-            opts.cg_ctl = cg_ctl
-            check(lib.gslm_matvec_view_ex(ctypes.byref(vr.view), ctypes.byref(g), ctypes.byref(vs),
-                                          loc.weights[k].data_ptr(), 1, vr.geom.data_ptr(), vr.binning.data_ptr(),
-                                          vr.N, vr.image.data_ptr(), vr.scratch.data_ptr(), vr.scratch.numel(),
-                                          ctypes.byref(vs), ctypes.byref(opts), loc.stream), "gslm_matvec_view_ex")
+            vr.product(g, vs, loc.weights[k].data_ptr(), 1, vs, opts, loc.stream, "gslm_matvec_view_ex")
             vr.tail_clean = True
             if overlap:  # 4. (pipelined) view k's screen sums leave while view k+1 renders
                 swork.append(self._all_to_all_async(b["screen_recv"][k], b["screen_send"][k]))
@@ -694,15 +652,10 @@ class GaussianShardedOperator:
             if R is not None:
                 opts.rest_basis, opts.rest_views, opts.view_base = R.data_ptr(), self.rest_views, c0
             if fuse and c1 == nv:
-                opts.dot_vy = dot_out
-                opts.dot_scratch = loc.dot_scratch.data_ptr()
-                opts.dot_scratch_bytes = loc.dot_scratch.numel() * 8
-            vptr = ctypes.cast(ctypes.byref(self.views_kt, c0 * vsz), ctypes.POINTER(_lib.GslmView))
-            check(lib.gslm_gather_screen(vptr, c1 - c0, ctypes.byref(gs), b["screen_recv"].data_ptr() + 32 * c0 * S,
-                                         ctypes.byref(vs), ctypes.byref(ys), ctypes.byref(opts), loc.stream),
-                  "gslm_gather_screen")
-        e0, e1 = self.layout.offsets["exposure"]
-        if e1 > e0:
-            torch.mul(v[e0:e1], float(self._damps[6]), out=y[e0:e1])  # J has no exposure column
+                self._dot_opts(opts, dot_out)
+            check(lib.gslm_gather_screen(_lib.view_ptr(self.views_kt, c0), c1 - c0, ctypes.byref(gs),
+                                         b["screen_recv"].data_ptr() + 32 * c0 * S, ctypes.byref(vs), ctypes.byref(ys),
+                                         ctypes.byref(opts), loc.stream), "gslm_gather_screen")
+        self._exposure_tail(v, y)
         self._mark(5)
         return fuse
