@@ -994,6 +994,47 @@ int gslm_matvec_view_active(const gslm_view* view, const gslm_gaussians* gi, con
                      active_ids, n_active, active_rows, stream);
 }
 
+// diag(2 J^T diag(w) J [+ D]) of the matrix gslm_matvec_view_ex applies (solver_functions.py:83-132), one view
+int gslm_lm_diag_view(const gslm_view* view, const gslm_gaussians* gi, const float* pixel_weight, int32_t mask_xyz,
+                      const void* geom, const void* binning, int64_t N, const void* image, void* scratch,
+                      size_t scratch_bytes, const gslm_grads* diag, const double* damp7, int32_t flags, void* stream) {
+  // every check before any launch: an error return leaves the destination untouched
+  if (!mask_xyz) {
+    set_error("lm_diag_view: the diagonal is the LM rows' (mask_xyz = 1: no colour x geometry cross terms)");
+    return GSLM_ERR_INVALID;
+  }
+  if (!pixel_weight || !diag) {
+    set_error("lm_diag_view: NULL pixel_weight or destination");
+    return GSLM_ERR_INVALID;
+  }
+  if (flags & ~(GSLM_DIAG_TAIL_CLEAN | GSLM_DIAG_ACCUMULATE | GSLM_DIAG_SH_REST_PROJECTED)) {
+    set_error("lm_diag_view: unknown flag bits");
+    return GSLM_ERR_INVALID;
+  }
+  if (!view || !gi || !geom || !image || !scratch || N < 0 || (N > 0 && !binning)) {
+    set_error("lm_diag_view: NULL view, gaussians or workspace, or a negative pair count");
+    return GSLM_ERR_INVALID;
+  }
+  Bound b;
+  int st = bind_all(view, gi, geom, binning, N, image, scratch, scratch_bytes, &b);
+  if (st) return st;
+  if (!b.g.raw || b.g.cov3D || b.g.colors) {
+    set_error("lm_diag_view: gaussians must be the raw GaussianModel leaves with SH colours");
+    return GSLM_ERR_INVALID;
+  }
+  const bool proj = (flags & GSLM_DIAG_SH_REST_PROJECTED) && b.g.M > 1;
+  const int64_t R = proj ? 3 : 3 * (b.g.M - 1);
+  if ((diag->sh_dc && diag->sh_dc_stride != 3) || (diag->sh_rest && b.g.M > 1 && diag->sh_rest_stride != R)) {
+    set_error("lm_diag_view: the destination is a flat param-space vector (dc stride 3, rest stride 3(M-1), or 3 "
+              "projected)");
+    return GSLM_ERR_INVALID;
+  }
+  DebugScope dbg_scope(view->debug != 0, stream);
+  return launch_lm_diag(b.v, b.g, b.gb, b.bb, b.ib, b.sb, N, pixel_weight, make_gradk(diag), damp7,
+                        !(flags & GSLM_DIAG_ACCUMULATE), proj, (flags & GSLM_DIAG_TAIL_CLEAN) != 0,
+                        (hipStream_t)stream);
+}
+
 // The list-order parameter block: [xyz 3 | raw scale 3 | raw rotation 4 | raw opacity 1] floats and the clamp
 // word, each an array over the na listed Gaussians -- everything chain_jvp / chain_vjp load per Gaussian on the LM
 // rows (xyz frozen: the primal SH coefficients are not read).

@@ -682,4 +682,9 @@ int launch_active_pack(bool to_active, const float* src, float* dst, const int32
                        const int32_t* widths, int ngroups, int64_t tail_n, hipStream_t s);
 int launch_sh_rest_project(const ViewK& v, const GaussK& g, int mode, const float* in, int64_t in_stride, float* out,
                            int64_t out_stride, hipStream_t s);
+// diag(2 J^T diag(weight) J [+ D]) of one view on the LM rows (gslm_lm_diag_view, lm_diag.hip): the tile pass into
+// the head rows of sb.contrib (the row map built first unless tail_clean), then the per-Gaussian gather into y
+int launch_lm_diag(const ViewK& v, const GaussK& g, const GeomBufs& gb, const BinBufs& bb, const ImgBufs& ib,
+                   const ScratchBufs& sb, int64_t N, const float* weight, const GradK& y, const double* damp7,
+                   bool overwrite, bool rest_proj, bool tail_clean, hipStream_t s);
 }  // namespace gslm

@@ -33,6 +33,9 @@ MV_TAIL_CLEAN = 1  # gslm_matvec_opts.flags: GSLM_MV_TAIL_CLEAN
 MV_SH_REST_PROJECTED = 2  # GSLM_MV_SH_REST_PROJECTED
 MV_LEAN = 4  # GSLM_MV_LEAN
 MV_EXPOSURE = 8  # GSLM_MV_EXPOSURE
+DIAG_TAIL_CLEAN = 1  # gslm_lm_diag_view flags: GSLM_DIAG_TAIL_CLEAN
+DIAG_ACCUMULATE = 2  # GSLM_DIAG_ACCUMULATE
+DIAG_SH_REST_PROJECTED = 4  # GSLM_DIAG_SH_REST_PROJECTED
 
 DEFAULT_DAMP = {"xyz": 5e2, "features_dc": 5e-2, "features_rest": 5e-2, "scaling": 5e-2, "rotation": 5e-2,
                 "opacity": 5e-2, "exposure": 1e1}
@@ -836,6 +839,39 @@ class LMProblem(_ProductOpts):
     def zeros(self):
         return torch.zeros(self.layout.numel, dtype=torch.float32, device=self.device)
 
+    # -------------------------------------------------------------- diag(J^T W J + D)  (cgls_jacobi)
+    def diagonal(self, out=None, damp=True):
+        """out = diag(sum_b 2 J_b^T W_b J_b [+ D]) in this problem's layout (projected when sh_projection selected
+        it, else the reference's): gslm_lm_diag_view per view, the first overwriting and the others accumulating, D
+        added once; the exposure tail is D alone.  Needs a current evaluate() (the weights); reuses each view's LM row
+        map when it has one and builds it otherwise (the products after it then reuse it).  The plain residual on the
+        LM rows only: ValueError with mask_xyz=False, ssim, train_exposure, or the batched problem's coordinates."""
+        if (not self.mask_xyz or self.ssim or self.train_exposure or self.layout.rest_views or
+                self._active is not None):
+            raise ValueError("diagonal: the [r; r] residual on the LM rows (mask_xyz=True, no SSIM, no trained "
+                             "exposure), in the full or the single-view projected layout")
+        if any(w is None for w in self.weights):
+            raise RuntimeError("diagonal: no current evaluate() (the per-pixel weights)")
+        out = torch.empty(self.layout.numel, dtype=torch.float32, device=self.device) if out is None else out
+        g = raw_gaussians(self.model)
+        ys = self.layout.grads_struct(out)
+        for b, vr in enumerate(self.views):
+            flags = ((DIAG_TAIL_CLEAN if vr.tail_clean else 0) | (DIAG_ACCUMULATE if b else 0) |
+                     (DIAG_SH_REST_PROJECTED if self.layout.rest_projected else 0))
+            check(lib.gslm_lm_diag_view(ctypes.byref(vr.view), ctypes.byref(g), self.weights[b].data_ptr(), 1,
+                                        vr.geom.data_ptr(), vr.binning.data_ptr(), vr.N, vr.image.data_ptr(),
+                                        vr.scratch.data_ptr(), vr.scratch.numel(), ctypes.byref(ys),
+                                        self._damps if (damp and b == 0) else None, flags, self.stream),
+                  "gslm_lm_diag_view")
+            vr.tail_clean = True
+        if not self.views:
+            for k, name in enumerate(GROUPS[:6]):
+                o0, o1 = self.layout.offsets[name]
+                out[o0:o1].fill_(float(self._damps[k]) if damp else 0.0)
+        e0, e1 = self.layout.offsets["exposure"]
+        out[e0:e1].fill_(float(self._damps[6]) if damp else 0.0)
+        return out
+
 
 class BatchedLMProblem(LMProblem, _StageTimes):
     """LMProblem over several views with one batched pass per product and per J^T b on one GPU (the reference's
@@ -1364,6 +1400,111 @@ def cgls_fused(prob, g, max_iter=10, restart_iter=10, tol=1e-10, atol=0.0, check
         history = c[4:4 + min(nh, max_iter)]
         return x, {"iters": iter_total, "residuals": history, "stop": int(c[0])}
     return x, {"iters": iter_total, "residuals": history}
+
+
+def cgls_jacobi(prob, g, max_iter=10, restart_iter=10, tol=1e-10, atol=0.0, check_every=True, verbose=False,
+                diag=None):
+    """cgls_fused's solve of (J^T J + D) x = g from x0 = 0 with the Jacobi preconditioner M = diag(J^T J + D)
+    (LMProblem.diagonal): the reference's restart schedule and stopping tests (conjugate_gradient.py:51-127) with
+    z = M^-1 s, gamma = <s, z> and p = z + beta p.  The monitor b^2 - <x, g> - <x, s> is the objective itself and
+    does not change.  Returns (x, info).
+
+    Scalars stay on the device (gslm_pcg_update, gslm_xpby_dev); with check_every=True the stopping tests read them
+    back every iteration, with check_every=False the loop has no host synchronisation (one read-back after it, for
+    the NaN check).  diag: the diagonal in prob's layout when the caller has it (entries <= 0 are not preconditioned
+    against: z = 0 there); ones make this plain CG.  A local single-view problem is solved on its active list as in
+    cgls_fused (the diagonal packed with g; GSLM_CG_ACTIVE=0 keeps the full vectors).  The lean loop is not
+    involved.  The plain residual on the LM rows only (LMProblem.diagonal's ValueError otherwise)."""
+    if not isinstance(prob, LMProblem) or prob.ssim or prob.train_exposure or not prob.mask_xyz or \
+            prob.layout.rest_views:
+        raise ValueError("cgls_jacobi: a local LMProblem with the [r; r] residual on the LM rows (mask_xyz=True, no "
+                         "SSIM, no trained exposure, not the batched problem)")
+    if diag is None:
+        diag = prob.diagonal()
+    act = _active_view_for(prob, g, None)
+    if act is not None:
+        gp = act.pack(g)
+        if prob.exposure_is_zero(g):
+            act._mark_rhs(gp)
+        x, info = _pcg(act, gp, act.pack(diag), max_iter, restart_iter, tol, atol, check_every, verbose)
+        return act.unpack(x), info
+    return _pcg(prob, g, diag, max_iter, restart_iter, tol, atol, check_every, verbose)
+
+
+def _pcg(prob, g, diag, max_iter, restart_iter, tol, atol, check_every, verbose):
+    """cgls_jacobi's recursion on the vectors of `prob` (the problem itself or its active view)."""
+    n = prob.layout.numel
+    dev, st = prob.device, prob.stream
+    lo = (3 * prob.layout.P // 4) * 4  # (mask_xyz: the xyz group is zero in every iterate, as in cgls_fused)
+    na = n - lo
+    off = lambda t: t.data_ptr() + 4 * lo
+    sc = torch.zeros(16, dtype=torch.float64, device=dev)
+    ptr = lambda i: sc.data_ptr() + 8 * i
+    GAM, GAMN, DEL, XG, XS = 0, 1, 2, 3, 4
+    x, q, z, minv = (torch.zeros(n, dtype=torch.float32, device=dev) for _ in range(4))
+    s, p = torch.empty_like(x), torch.empty_like(x)
+    check(lib.gslm_precond_invert(na, off(diag), off(minv), st), "gslm_precond_invert")
+    b2 = float(prob.loss) if check_every else None  # ||b||^2 = loss
+    ez = {"exposure_zero": True} if prob.exposure_is_zero(g) else {}
+    iter_total, last_res, history = 0, math.inf, []
+    first = True
+    while iter_total < max_iter:
+        if first:
+            s.copy_(g)  # s0 = J^T b - A x0 with x0 = 0
+            first = False
+        else:
+            prob.matvec(x, q)
+            torch.sub(g, q, out=s)
+        torch.mul(s[lo:], minv[lo:], out=z[lo:])
+        p.copy_(z)
+        prob.dot(s[lo:], z[lo:], ptr(GAM))
+        stop = False
+        beta = None  # (num, den) of the direction update not yet applied
+        for _ in range(restart_iter):
+            if beta is not None:
+                check(lib.gslm_xpby_dev(na, off(z), beta[0], beta[1], off(p), st), "gslm_xpby_dev")
+            if not prob.matvec_dot(p, q, ptr(DEL), **ez):
+                prob.dot(p[lo:], q[lo:], ptr(DEL))
+            if check_every:
+                delta = sc[DEL].item()
+                if not math.isfinite(delta):
+                    raise_nonfinite(prob, g)
+                if delta < 1e-20:
+                    if verbose:
+                        print("Early termination: delta is too small.")
+                    stop = True
+                    break
+            # x += alpha p ; s -= alpha q ; z = M^-1 s ; gamma' = <s, z>  (one pass)
+            check(lib.gslm_pcg_update(na, ptr(GAM), ptr(DEL), off(p), off(q), off(x), off(s), off(minv), off(z),
+                                      prob.dot_scratch.data_ptr(), ptr(GAMN), st), "gslm_pcg_update")
+            beta = (ptr(GAMN), ptr(GAM))  # beta = gamma' / gamma; after the swap below the GAM / GAMN slots
+            if check_every:
+                prob.dot(x[lo:], g[lo:], ptr(XG))
+                prob.dot(x[lo:], s[lo:], ptr(XS))
+                vals = sc[:5].tolist()
+                if not all(math.isfinite(vals[k]) for k in (GAM, GAMN, XG, XS)):
+                    raise_nonfinite(prob, g)
+                res = b2 - vals[XG] - vals[XS]  # the monitor of conjugate_gradient.py:103-104
+                history.append(res)
+                if verbose:
+                    print(f"[Iter {iter_total + 1}] res: {res:.2e}")
+                if res > last_res:
+                    stop = True
+                    break
+                last_res = res
+                if vals[GAMN] < max(tol * math.sqrt(max(vals[GAM], 0.0)), atol):
+                    stop = True
+                    break
+            GAM, GAMN = GAMN, GAM
+            iter_total += 1
+            if iter_total >= max_iter:
+                stop = True
+                break
+        if stop:
+            break
+    if not check_every and not all(math.isfinite(v) for v in sc[:3].tolist()):  # the solve's one read-back
+        raise_nonfinite(prob, g)
+    return x, {"iters": iter_total, "residuals": history, "precond": "jacobi"}
 
 
 def cgls_residual(prob, max_iter=10, restart_iter=10, tol=1e-10, atol=0.0, verbose=False, callback=None):
@@ -1948,7 +2089,7 @@ def clear_val_cache():
 def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, mask_xyz=True, check_every=True,
             verbose=False, device="cuda", sh_projection="auto", recursion="fused", exchange="auto", group=None,
             val_batch=8, timing=False, backend=None, line_search="union", val_at_start=False, cache_val=True,
-            multiview="loop", union_active=False, train_exposure=False, val_exposure="forward"):
+            multiview="loop", union_active=False, train_exposure=False, val_exposure="forward", precond=None):
     """One LM step of train_jvp.py:237-289: loss, CGLS on the normal equations, backtracking line search.
 
     Single process: LMProblem over `cams` (with one training view the SH-rest group of the CG vectors is carried
@@ -1985,6 +2126,10 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     exposure in the loss blend's epilogue (LossEvaluator(fused_exposure=True)): the validation runs in batches over the
     side streams, and line_search="union" snapshots the six points with their exposure and evaluates them through one
     binning per view; line_search="exact" runs the fused evaluation seven times.
+    precond: None (cgls_fused, today's step launch for launch) or "jacobi" (cgls_jacobi: CG preconditioned with
+    diag(J^T J + D), LMProblem.diagonal; the result and its cg info report precond="jacobi").  Any other string raises
+    ValueError, and so does "jacobi" with recursion="cgls", train_exposure=True, multiview="batched", a sharded run,
+    mask_xyz=False or a backend (the SSIM residual, which lm_step does not run, is refused by cgls_jacobi itself).
     backend: (problem_cls, evaluator_cls, solver) replacing (LMProblem, LossEvaluator, cgls_fused) -- the CPU
     multi-process tests run this same driver, sharding and reductions on the oracle restatement."""
     import time
@@ -2009,6 +2154,14 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
         raise ValueError(f"val_exposure must be 'forward' or 'fused', got {val_exposure!r}")
     if val_exposure == "fused" and not train_exposure:
         raise ValueError("val_exposure='fused' is an option of train_exposure=True")
+    if precond not in (None, "jacobi"):
+        raise ValueError(f"precond must be None or 'jacobi', got {precond!r}")
+    if precond == "jacobi":
+        if (sharded or backend is not None or recursion != "fused" or not mask_xyz or train_exposure or
+                multiview == "batched"):
+            raise ValueError("precond='jacobi' is the single-process step with multiview='loop', recursion='fused', "
+                             "mask_xyz=True and no trained exposure")
+        solver = cgls_jacobi
     exp_kw = {"train_exposure": True} if train_exposure else {}
     fused_exposure = val_exposure == "fused"
     t = {}
@@ -2117,6 +2270,8 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     lap("line_search_ms")
     out = dict(start_loss=start_loss, final_val_loss=final, best_alpha=best_alpha, cg=info, step=s, trace=trace,
                val_views=len(val_cams), ranks=n if sharded else 1, line_search="union" if union else "exact")
+    if precond is not None:
+        out["precond"] = precond
     if val_at_start:
         out["val_start_loss"] = val_start
     if union and getattr(val, "union_counts", None):

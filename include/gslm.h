@@ -693,6 +693,42 @@ int gslm_dot_finalize(const void* partials, int32_t np, double* out_dev, void* s
 int gslm_damp_add(int64_t n, const float* x, const int64_t* group_bounds, const double* group_damp,
                   int32_t ngroups, float* y, void* stream);
 
+/* ---- diag(J^T W J + D) and Jacobi-preconditioned CG (additive entry points, still ABI 9) ----
+ * gslm_lm_diag_view: the diagonal of the matrix gslm_matvec_view_ex applies for one view with mask_xyz (the
+ * reference's matvec / matvec_T pair, solver/solver_functions.py:83-132, on the [r; r] residual):
+ *   diag = 2 J^T diag(pixel_weight) J [+ D],
+ * written into the groups of `diag` (a flat param-space vector as gslm_matvec_view_ex's y: sh_dc_stride 3,
+ * sh_rest_stride 3(M-1), or 3 with GSLM_DIAG_SH_REST_PROJECTED -- coordinate c of the projected group gets
+ * |B_rest|^2 S_col[c]; a NULL group is not written).  The derivative of alpha is the product's own (d alpha / d o = G,
+ * d alpha / d power = o G, the 0.99 clamp ignored), so this is the diagonal of that operator exactly.  With the view
+ * direction frozen no parameter moves both the colour and the conic / opacity: a tile pass sums twelve values per
+ * head entry of the LM row map (9 geometry monomials, 3 colour sums; 48 bytes, the scratch's gradient rows hold
+ * them) and a per-Gaussian pass applies the chains.  The xyz group gets D alone, and so does a Gaussian without a
+ * head row.  damp7 (host, GaussianModelDampMatrix order) or NULL: D is added per group (pass it for one view of a
+ * sum over views).  flags: GSLM_DIAG_TAIL_CLEAN -- the LM row map of this geometry is current (as GSLM_MV_TAIL_CLEAN;
+ * without it the call builds the map, after which the flag may be passed to the products too);
+ * GSLM_DIAG_ACCUMULATE -- add into diag instead of overwriting it.  The scratch's gradient rows are overwritten
+ * (every product rewrites its own).  No float atomics: bitwise reproducible.
+ * GSLM_ERR_INVALID, before anything is launched, for mask_xyz = 0, a NULL pixel_weight or diag, unknown flags,
+ * non-raw gaussians or a destination with other strides; GSLM_ERR_CAPACITY for a scratch below
+ * gslm_scratch_bytes(P, num_rendered) (which covers 48 bytes per head row).  On an error the outputs are untouched. */
+#define GSLM_DIAG_TAIL_CLEAN 1
+#define GSLM_DIAG_ACCUMULATE 2
+#define GSLM_DIAG_SH_REST_PROJECTED 4
+int gslm_lm_diag_view(const gslm_view* view, const gslm_gaussians* g, const float* pixel_weight, int32_t mask_xyz,
+                      const void* geom, const void* binning, int64_t num_rendered, const void* image, void* scratch,
+                      size_t scratch_bytes, const gslm_grads* diag, const double* damp7, int32_t flags,
+                      void* stream);
+/* One preconditioned CG step, a = gam / del read from device memory:  x += a p (x == NULL: skipped, p not read);
+ * s -= a q;  z = s (.) minv;  *gam_new_dev = <s, z> (scratch >= gslm_dot_scratch_bytes(n)).  Vectors 16-byte
+ * aligned.  gslm_cg_update's element order and double partial sums: with minv = 1 the results are bitwise its own.
+ * The direction update p = z + beta p is gslm_xpby_dev. */
+int gslm_pcg_update(int64_t n, const double* gam_dev, const double* del_dev, const float* p, const float* q,
+                    float* x, float* s, const float* minv, float* z, void* scratch, double* gam_new_dev,
+                    void* stream);
+/* minv[j] = 1 / m[j], or 0 where m[j] <= 0 (or NaN): the Jacobi preconditioner of a diagonal m. */
+int gslm_precond_invert(int64_t n, const float* m, float* minv, void* stream);
+
 /* ---- RCCL collectives over xGMI, communicator handle passed in (SURVEY 8(b) "gslm_allreduce*", 8(e)) ----
  * The reference has no multi-GPU code (its LinearSolverFunctions renders a view batch serially on one GPU,
  * solver/solver_functions.py:88-93,110-121); these replace the all-reduce of J^T r / J^T J v and of the CG scalars

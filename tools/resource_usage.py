@@ -10,7 +10,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "gaussian-splatting-lm_amd", "csrc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-ffp-contract=off", "-munsafe-fp-atomics",
          "-I../../include", "-I.", "-Rpass-analysis=kernel-resource-usage", "--cuda-device-only", "-c", "-o", os.devnull]
-TILE = {"jvp.hip", "backward.hip", "render_fwd.hip"}  # -fno-slp-vectorize, as the Makefile
+TILE = {"jvp.hip", "backward.hip", "render_fwd.hip", "lm_diag.hip"}  # -fno-slp-vectorize, as the Makefile
 
 
 def demangle(names):
