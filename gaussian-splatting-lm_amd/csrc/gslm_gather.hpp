@@ -22,12 +22,13 @@ struct FlatK {
 // one contiguous range (row_slot groups rows by Gaussian index), streamed through LDS in chunks of
 // GATHER_CHUNK rows with coalesced float4 loads; each thread then adds its own rows from LDS, in the
 // same order as sum_rows (bitwise-identical sums).  Must be called by all 256 threads.
+// NF: floats summed per row -- the NV gradient values, or all twelve of k_render_diag's three-float4 rows.
 constexpr int GATHER_CHUNK = 512;
-template <int ROWF4>
+template <int ROWF4, int NF = NV>
 __device__ __forceinline__ void block_sum_rows(const float4* __restrict__ rows, uint32_t R0, uint32_t R1,
-                                               uint32_t my_off, uint32_t my_n, float4* s_buf, float G2[NV]) {
+                                               uint32_t my_off, uint32_t my_n, float4* s_buf, float G2[NF]) {
 #pragma unroll
-  for (int q = 0; q < NV; ++q) G2[q] = 0.f;
+  for (int q = 0; q < NF; ++q) G2[q] = 0.f;
   const uint32_t my_end = my_off + my_n;
   for (uint32_t c0 = R0; c0 < R1; c0 += GATHER_CHUNK) {
     const uint32_t cn = min((uint32_t)GATHER_CHUNK, R1 - c0);
@@ -36,10 +37,10 @@ __device__ __forceinline__ void block_sum_rows(const float4* __restrict__ rows, 
     __syncthreads();
     const uint32_t lo = max(my_off, c0), hi = min(my_end, c0 + cn);
     for (uint32_t r = lo; r < hi; ++r) {
-      float t[NV];
-      load_row<ROWF4>(s_buf, r - c0, t);
+      float t[NF];
+      load_row<ROWF4, NF>(s_buf, r - c0, t);
 #pragma unroll
-      for (int q = 0; q < NV; ++q) G2[q] += t[q];
+      for (int q = 0; q < NF; ++q) G2[q] += t[q];
     }
   }
   __syncthreads();  // s_buf may be reused by the caller

@@ -1,5 +1,12 @@
 // gslm_tile.hpp -- per-tile back-to-front (VJP) pass shared by the drop-in backward and the fused
-// LM matvec kernels.
+// LM matvec kernels, and the parts of that pass that k_render_diag (lm_diag.hip) is written with too:
+//   tile_pix          the tile / pixel prologue of a tile kernel
+//   wave_bounds       the per-wave n_contrib bounds and the number of list positions worth a visit
+//   stage_entry       one list entry's record into the batch's five float2 planes, its quadrant mask refined
+//   load_visit        entry j of the five planes
+//   primal_test       a visit's alpha and its skip decisions, rounded exactly as the forward's
+//   combine_waves     one value slot's four per-wave partials, in fixed quadrant order
+// Each pass keeps its own loop nest (rounds, hit words, visits) and calls these in place.
 //
 // VJP accumulation strategy (MI355X-specific): instead of upstream's per-pixel global atomicAdd
 // (10 atomics per pixel-Gaussian pair), every wave reduces a Gaussian's per-pixel contributions
@@ -32,9 +39,8 @@ __device__ __forceinline__ float wave_sum_lane63(float x) {
 // gfx950 permlane swaps for the cross-half steps and DPP inside rows.  On return every lane of the
 // 8-lane group k (lanes 8k..8k+7) holds sum over the wave of v[k].  18 instructions instead of
 // 8 x 6 DPP adds.  Requires all 64 lanes active.
-__device__ __forceinline__ float perm32_add(float a, float b, float& hi_part) {
+__device__ __forceinline__ float perm32_add(float a, float b) {
   const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(a), __float_as_uint(b), false, false);
-  (void)hi_part;
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 __device__ __forceinline__ float perm16_add(float a, float b) {
@@ -42,10 +48,9 @@ __device__ __forceinline__ float perm16_add(float a, float b) {
   return __uint_as_float(r[0]) + __uint_as_float(r[1]);
 }
 __device__ __forceinline__ float wave_reduce8_t(const float v[8], int lane) {
-  float dummy = 0.f;
   // step 1 (lanes l <-> l+32): lower half keeps values 0..3, upper half values 4..7
-  const float w0 = perm32_add(v[0], v[4], dummy), w1 = perm32_add(v[1], v[5], dummy);
-  const float w2 = perm32_add(v[2], v[6], dummy), w3 = perm32_add(v[3], v[7], dummy);
+  const float w0 = perm32_add(v[0], v[4]), w1 = perm32_add(v[1], v[5]);
+  const float w2 = perm32_add(v[2], v[6]), w3 = perm32_add(v[3], v[7]);
   // step 2 (rows r <-> r^1): even rows keep w0, w1; odd rows keep w2, w3
   const float u0 = perm16_add(w0, w2), u1 = perm16_add(w1, w3);
   // step 3 (lanes l <-> l^8 inside a row): bit3 = 0 keeps u0, bit3 = 1 keeps u1
@@ -94,6 +99,124 @@ __device__ __forceinline__ int wave_max_u(int x) {
   return x;
 }
 
+// The tile / pixel prologue of a tile kernel (blockDim = 256): the block's tile in launch order, the thread's pixel
+// (tile_pixel: wave w on quadrant w) and its index in a [H, W] plane; pid is only valid where inside.
+struct TilePix {
+  int tile, tile_x, tile_y, px, py;
+  bool inside;
+  int64_t pid;
+};
+__device__ __forceinline__ TilePix tile_pix(const ViewK& v, const uint32_t* __restrict__ tile_order) {
+  TilePix p;
+  p.tile = (int)tile_order[blockIdx.x];
+  p.tile_x = p.tile % v.gx;
+  p.tile_y = p.tile / v.gx;
+  tile_pixel(p.tile_x, p.tile_y, threadIdx.x, p.px, p.py);
+  p.inside = p.px < v.W && p.py < v.H;
+  p.pid = (int64_t)p.py * v.W + p.px;
+  return p;
+}
+
+// Per-wave bounds of a block-cooperative tile pass: wave w's lanes blend nothing at list positions >= wm[w] (the
+// largest n_contrib of its pixels; `last` is 0 outside the image), and positions >= n_eff are visited by no wave.
+// n_contrib counts positions of the tile's own list, so it never exceeds the range length and the clamp changes
+// nothing for the forward's own buffers; it is kept in the one form all passes share so that no n_contrib, whatever
+// its source, can take a pass off the end of the list.  s_misc: 4 ints of LDS; the caller orders it after earlier
+// uses of that LDS.  One block barrier.
+struct WaveBounds {
+  int wm0, wm1, wm2, wm3, n_eff;
+  // the waves that still blend at list position pos, as a quadrant mask
+  __device__ __forceinline__ uint32_t blending(int pos) const {
+    return (pos < wm0 ? 1u : 0u) | (pos < wm1 ? 2u : 0u) | (pos < wm2 ? 4u : 0u) | (pos < wm3 ? 8u : 0u);
+  }
+};
+__device__ __forceinline__ WaveBounds wave_bounds(uint32_t last, uint2 range, int* s_misc) {
+  const int wmax = wave_max_u((int)last);
+  if ((threadIdx.x & 63) == 0) s_misc[threadIdx.x >> 6] = wmax;
+  __syncthreads();
+  WaveBounds b;
+  b.wm0 = s_misc[0];
+  b.wm1 = s_misc[1];
+  b.wm2 = s_misc[2];
+  b.wm3 = s_misc[3];
+  b.n_eff = min(max(max(b.wm0, b.wm1), max(b.wm2, b.wm3)), (int)(range.y - range.x));
+  return b;
+}
+
+// The back-to-front passes stage a batch's records as five float2 planes of BATCH entries ((x, y), (conic a, b),
+// (conic c, opacity), (r, g), (b, 1/depth)): a visit reads entry j of each plane from ONE address (8 j) with plane
+// offsets -- two ds_read2st64_b64 and a ds_read_b64, issued together -- where float4 / float2 arrays needed two
+// addresses of different scale and the float2 read waited behind the float4 pair.
+// stage_entry: thread i of the batch stages the entry at list position pos into entry i of the planes and returns its
+// quadrant mask, restricted to the waves that still blend at pos; g is its Gaussian.
+template <int BATCH>
+__device__ __forceinline__ uint32_t stage_entry(const uint32_t* __restrict__ point_list, uint32_t first, int pos,
+                                                const float4* __restrict__ rec, const WaveBounds& wb, float2* s_rp,
+                                                int i, uint32_t& g) {
+  const uint32_t e = point_list[first + pos];
+  g = pl_id(e);
+  const float4 r0 = rec[RECS * (int64_t)g + 0], r1 = rec[RECS * (int64_t)g + 1], r2 = rec[RECS * (int64_t)g + 2];
+  s_rp[i] = make_float2(r0.x, r0.y);
+  s_rp[BATCH + i] = make_float2(r0.z, r0.w);
+  s_rp[2 * BATCH + i] = make_float2(r1.x, r1.y);
+  s_rp[3 * BATCH + i] = make_float2(r1.z, r1.w);
+  s_rp[4 * BATCH + i] = make_float2(r2.x, r2.y);
+  return pl_mask(e) & wb.blending(pos);
+}
+
+struct VisitRec {
+  float2 xy, ab, co, rg, bd;  // (x, y), (conic a, b), (conic c, opacity), (r, g), (b, 1/depth)
+};
+template <int BATCH>
+__device__ __forceinline__ VisitRec load_visit(const float2* s_rp, int j) {
+  VisitRec r;
+  r.xy = s_rp[j];
+  r.ab = s_rp[BATCH + j];
+  r.co = s_rp[2 * BATCH + j];
+  r.rg = s_rp[3 * BATCH + j];
+  r.bd = s_rp[4 * BATCH + j];
+  return r;
+}
+
+// The primal side of one visit: the lane's alpha of the entry and whether it blends it.  These tests (power, alpha)
+// must round exactly as the forward's -- the same visits are blended in every pass (-ffp-contract=off; no FMA here) --
+// and the list position is tested against the primal's n_contrib (`last`, 0 outside the image) instead of a running
+// transmittance.  any: some lane of the wave blends it (per-condition ballots fold into their compares' lane masks:
+// no VGPR round trip of `valid`).
+struct Primal {
+  float dx, dy, G, alpha;
+  bool valid, any;
+};
+__device__ __forceinline__ Primal primal_test(const VisitRec& r, float pxf, float pyf, uint32_t contributor,
+                                              uint32_t last) {
+  Primal p;
+  p.dx = r.xy.x - pxf;
+  p.dy = r.xy.y - pyf;
+  const float power = gpower(r.ab.x, r.ab.y, r.co.x, p.dx, p.dy);
+  p.G = gexp(power);
+  p.alpha = fminf(0.99f, r.co.y * p.G);
+  const bool c_last = contributor < last, c_pow = !(power > 0.0f), c_alpha = p.alpha >= 1.0f / 255.0f;
+  p.valid = c_last && c_pow && c_alpha;
+  p.any = (__builtin_amdgcn_ballot_w64(c_last) & __builtin_amdgcn_ballot_w64(c_pow) &
+           __builtin_amdgcn_ballot_w64(c_alpha)) != 0ull;
+  return p;
+}
+
+// Value slot sq of batch element i, summed over the four waves' partials s_acc[wave][slot][element] in fixed quadrant
+// order.  Every wave's slot is read and the ones it never wrote (no hit: mask bit clear) dropped by a select -- exactly
+// the zero a visit with no valid lane would have stored: plain LDS loads and v_cndmask instead of an exec-mask branch
+// around each load.
+template <int NSLOT, int STRIDE>
+__device__ __forceinline__ float combine_waves(const float* s_acc, int sq, int i, uint32_t mask) {
+  const float a0 = s_acc[(0 * NSLOT + sq) * STRIDE + i], a1 = s_acc[(1 * NSLOT + sq) * STRIDE + i];
+  const float a2 = s_acc[(2 * NSLOT + sq) * STRIDE + i], a3 = s_acc[(3 * NSLOT + sq) * STRIDE + i];
+  const float p0 = (mask & 1u) ? a0 : 0.f;
+  const float p1 = (mask & 2u) ? a1 : 0.f;
+  const float p2 = (mask & 4u) ? a2 : 0.f;
+  const float p3 = (mask & 8u) ? a3 : 0.f;
+  return ((p0 + p1) + p2) + p3;
+}
+
 // Screen-space gradient of one (tile, Gaussian) pair, value index q:
 //   0 dL/dx_pix  1 dL/dy_pix  2 dL/dconic.a  3 dL/dconic.b  4 dL/dconic.c  5 dL/dopacity_eff
 //   6..8 dL/drgb  9 dL/dinvdepth
@@ -128,12 +251,18 @@ __device__ __forceinline__ void store_row(float4* __restrict__ rows, uint32_t sl
   }
 }
 
-template <int ROWF4>
-__device__ __forceinline__ void load_row(const float4* __restrict__ rows, size_t slot, float t[NV]) {
+// NF = 12 (ROWF4 = 3 only): all twelve floats of the row (k_render_diag's rows)
+template <int ROWF4, int NF = NV>
+__device__ __forceinline__ void load_row(const float4* __restrict__ rows, size_t slot, float t[NF]) {
+  static_assert(NF == NV || (NF == 12 && ROWF4 == 3), "rows hold ten values, or twelve in three float4");
   if (ROWF4 == 3) {
     const float4 a = rows[3 * slot + 0], b = rows[3 * slot + 1], c = rows[3 * slot + 2];
     t[0] = a.x; t[1] = a.y; t[2] = a.z; t[3] = a.w; t[4] = b.x; t[5] = b.y; t[6] = b.z; t[7] = b.w;
     t[8] = c.x; t[9] = c.y;
+    if constexpr (NF == 12) {
+      t[10] = c.z;
+      t[11] = c.w;
+    }
   } else {
     const float4 a = rows[2 * slot + 0], b = rows[2 * slot + 1];
     t[0] = 0.f; t[1] = 0.f; t[2] = a.x; t[3] = a.y; t[4] = a.z; t[5] = a.w; t[6] = b.x; t[7] = b.y;
@@ -179,46 +308,24 @@ constexpr int vjp_acc_floats() { return 4 * n_used<WITH_XY, WITH_INV>() * acc_st
 
 // Back-to-front pass over the tile's list (upstream BACKWARD::renderCUDA semantics), writing one
 // reduced row per (tile, Gaussian) pair.  Block-uniform control flow; requires blockDim = 256.
-// slots != NULL (the LM row map): rows exist for head entries only -- those some wave still blending at their list
-// position visits (a non-empty mask below) -- and the others are not written.
-// s_rp: the batch's records as five float2 planes of BATCH entries ((x, y), (conic a, b), (conic c, opacity), (r, g),
-// (b, 1/depth)): a visit reads entry j of each plane from ONE address (8 j) with plane offsets -- two
-// ds_read2st64_b64 and a ds_read_b64, issued together -- where the float4 / float2 arrays needed two addresses of
-// different scale and the float2 read waited behind the float4 pair.
+// Only the entries some wave still blending at their list position visits (a non-empty mask below) get their row
+// written.  slots != NULL (the LM row map): rows exist for those head entries only.  slots == NULL (the drop-in's
+// rectangle rows): the caller fills every row with zeros first (launch_render_bwd).
+// s_rp: the batch's five record planes (stage_entry), 5 BATCH float2.
 template <bool WITH_XY, bool WITH_INV, int ROWF4, int BATCH>
-__device__ __forceinline__ void vjp_tile(VjpPix& st, bool inside, float pxf, float pyf, int tile_x, int tile_y,
+__device__ __forceinline__ void vjp_tile(VjpPix& st, float pxf, float pyf, int tile_x, int tile_y,
                                          uint2 range, const uint32_t* __restrict__ point_list,
                                          const float4* __restrict__ rec, const uint32_t* __restrict__ slots,
                                          const uint2* __restrict__ rect, const uint32_t* __restrict__ goff,
                                          float2* s_rp, uint64_t* s_bits, float* s_acc, int* s_misc,
-                                         float4* __restrict__ rows, bool write_tail) {
+                                         float4* __restrict__ rows) {
   constexpr int NU = n_used<WITH_XY, WITH_INV>();
   constexpr int ACC_STRIDE = acc_stride<BATCH>();
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  // Positions >= max over pixels of n_contrib are never blended: their rows are zero.  The leading
-  // barrier lets s_misc alias LDS the caller used before this pass (k_render_matvec's JVP buffers).
+  // The leading barrier lets s_misc alias LDS the caller used before this pass (k_render_matvec's JVP buffers).
   __syncthreads();
-  const int wmax = wave_max_u((int)st.last);
-  if (lane == 0) s_misc[w] = wmax;
-  __syncthreads();
-  // per-wave bound: wave w's lanes blend nothing at list positions >= wm[w]
-  const int wm0 = s_misc[0], wm1 = s_misc[1], wm2 = s_misc[2], wm3 = s_misc[3];
-  const int n_eff = max(max(wm0, wm1), max(wm2, wm3));
-  if (write_tail) {
-    float z[NV];
-#pragma unroll
-    for (int q = 0; q < NV; ++q) z[q] = 0.f;
-    for (int64_t k = (int64_t)range.x + n_eff + tid; k < (int64_t)range.y; k += TILE_PIX) {
-      uint32_t slot;
-      if (slots) {
-        slot = slots[k];
-      } else {
-        const uint32_t g = pl_id(point_list[k]);
-        slot = row_slot(goff[g], rect[g], tile_x, tile_y);
-      }
-      store_row<ROWF4>(rows, slot, z);
-    }
-  }
+  const WaveBounds wb = wave_bounds(st.last, range, s_misc);
+  const int n_eff = wb.n_eff;
   const int rounds = (n_eff + BATCH - 1) / BATCH;
   for (int r = 0; r < rounds; ++r) {
     const int base = n_eff - 1 - r * BATCH;  // list position of batch element 0
@@ -227,21 +334,10 @@ __device__ __forceinline__ void vjp_tile(VjpPix& st, bool inside, float pxf, flo
     uint32_t my_slot = 0;
     uint32_t my_mask = 0u;
     if (tid < cnt) {
-      const uint32_t e = point_list[range.x + base - tid];
-      const uint32_t g = pl_id(e);
-      my_mask = pl_mask(e);
-      const float4 r0 = rec[RECS * (int64_t)g + 0], r1 = rec[RECS * (int64_t)g + 1], r2 = rec[RECS * (int64_t)g + 2];
-      s_rp[tid] = make_float2(r0.x, r0.y);
-      s_rp[BATCH + tid] = make_float2(r0.z, r0.w);
-      s_rp[2 * BATCH + tid] = make_float2(r1.x, r1.y);
-      s_rp[3 * BATCH + tid] = make_float2(r1.z, r1.w);
-      s_rp[4 * BATCH + tid] = make_float2(r2.x, r2.y);
-      // and only the waves that still blend at this list position
-      const int pos = base - tid;
-      my_mask &= (pos < wm0 ? 1u : 0u) | (pos < wm1 ? 2u : 0u) | (pos < wm2 ? 4u : 0u) | (pos < wm3 ? 8u : 0u);
+      uint32_t g;
+      my_mask = stage_entry<BATCH>(point_list, range.x, base - tid, rec, wb, s_rp, tid, g);
       // the row slot of an entry that gets a row (below): the LM row map, or the drop-in's rectangle slot
-      if (my_mask || (!slots && write_tail))
-        my_slot = slots ? slots[range.x + base - tid] : row_slot(goff[g], rect[g], tile_x, tile_y);
+      if (my_mask) my_slot = slots ? slots[range.x + base - tid] : row_slot(goff[g], rect[g], tile_x, tile_y);
     }
     // which waves' quadrants this element can touch; wave w visits only its hits, and the combine below
     // takes zero for the others (exactly what a visit with no valid lane would have produced)
@@ -256,42 +352,32 @@ __device__ __forceinline__ void vjp_tile(VjpPix& st, bool inside, float pxf, flo
       const int hb = (int)__builtin_ctzll(hits);
       hits = clear_bit(hits, hb);
       const int j = 64 * wd + hb;
-      const float2 p0 = s_rp[j], p1 = s_rp[BATCH + j], p2 = s_rp[2 * BATCH + j], p3 = s_rp[3 * BATCH + j];
-      const float2 c = s_rp[4 * BATCH + j];
-      const float4 a = make_float4(p0.x, p0.y, p1.x, p1.y), b = make_float4(p2.x, p2.y, p3.x, p3.y);
+      const VisitRec e = load_visit<BATCH>(s_rp, j);
       // the whole record in one LDS round trip at the top of the iteration (the empty asm pins the loads
       // here; otherwise the colour half is fetched after the alpha test, a second exposed LDS latency;
       // prefetching the next hit's record instead measured 9% slower: it costs issue slots, not latency)
-      asm volatile("" : : "v"(b.z), "v"(b.w), "v"(c.x), "v"(c.y));
+      asm volatile("" : : "v"(e.rg.x), "v"(e.rg.y), "v"(e.bd.x), "v"(e.bd.y));
       {
-        const uint32_t contributor = (uint32_t)(base - j);  // 0-based list position
-        const float dx = a.x - pxf, dy = a.y - pyf;
-        const float power = gpower(a.z, a.w, b.x, dx, dy);
-        const float G = gexp(power);
-        const float alpha = fminf(0.99f, b.y * G);
-        const bool c_last = contributor < st.last, c_pow = !(power > 0.0f), c_alpha = alpha >= 1.0f / 255.0f;
-        const bool valid = c_last && c_pow && c_alpha;  // st.last = 0 outside the image
+        const Primal pt = primal_test(e, pxf, pyf, (uint32_t)(base - j), st.last);  // base - j: 0-based list position
+        const float dx = pt.dx, dy = pt.dy;
+        const bool any = pt.any;
         // <colour, dL/dpix> for every lane (the colour is already in registers)
         float cd;
         {
 #pragma clang fp contract(fast)
-          cd = (b.z * st.dpix[0] + b.w * st.dpix[1]) + c.x * st.dpix[2];
-          if (WITH_INV) cd += c.y * st.dinv;
+          cd = (e.rg.x * st.dpix[0] + e.rg.y * st.dpix[1]) + e.bd.x * st.dpix[2];
+          if (WITH_INV) cd += e.bd.y * st.dinv;
         }
         // A visit some lane blends runs the body in every lane, an invalid lane with alpha = G = 0: its row
         // values are 0, T is unchanged (rcp(1) = 1) and its accumulation update adds 0 * (...).  No per-lane
         // branch and no zeroing of the row values per visit.
-        // (per-condition ballots fold into their compares' lane masks: no VGPR round trip of `valid`)
-        const bool any = (__builtin_amdgcn_ballot_w64(c_last) & __builtin_amdgcn_ballot_w64(c_pow) &
-                          __builtin_amdgcn_ballot_w64(c_alpha)) != 0ull;
         float gv[NV];
 #pragma unroll
         for (int q = 0; q < NV; ++q) gv[q] = 0.f;
-        const float a_e = valid ? alpha : 0.f;
-        const float G_e = valid ? G : 0.f;
+        const float a_e = pt.valid ? pt.alpha : 0.f;
+        const float G_e = pt.valid ? pt.G : 0.f;
         if (any) {
-          // Only the primal tests above (power, alpha) must round exactly as the forward's; the
-          // derivative arithmetic below decides nothing and is contracted to FMAs.
+          // the derivative arithmetic decides nothing (primal_test did) and is contracted to FMAs
 #pragma clang fp contract(fast)
           const float inv1ma = rcp_f(1.f - a_e);
           st.T = st.T * inv1ma;
@@ -365,25 +451,14 @@ __device__ __forceinline__ void vjp_tile(VjpPix& st, bool inside, float pxf, flo
     }
     __syncthreads();
     // rows only for the entries some wave visited: the LM rows (slots) exist for head entries only (k_row_flags); the
-    // drop-in's rectangle rows of every other entry are the zeros its caller filled the buffer with (write_tail = 0),
-    // or were written by the tail loop above (write_tail)
-    if (tid < cnt && (my_mask || (!slots && write_tail))) {
+    // drop-in's rectangle rows of every other entry are the zeros its caller filled the buffer with
+    if (tid < cnt && my_mask) {
       float t[NV];
 #pragma unroll
       for (int q = 0; q < NV; ++q) {
         t[q] = 0.f;
-        if (q_used<WITH_XY, WITH_INV>(q)) {
-          const int sq = q_slot<WITH_XY, WITH_INV>(q);
-          // every wave's slot read, the ones it never wrote (no hit) then dropped by a select: plain LDS loads and
-          // v_cndmask instead of an exec-mask branch around each load
-          const float a0 = s_acc[(0 * NU + sq) * ACC_STRIDE + tid], a1 = s_acc[(1 * NU + sq) * ACC_STRIDE + tid];
-          const float a2 = s_acc[(2 * NU + sq) * ACC_STRIDE + tid], a3 = s_acc[(3 * NU + sq) * ACC_STRIDE + tid];
-          const float p0 = (my_mask & 1u) ? a0 : 0.f;
-          const float p1 = (my_mask & 2u) ? a1 : 0.f;
-          const float p2 = (my_mask & 4u) ? a2 : 0.f;
-          const float p3 = (my_mask & 8u) ? a3 : 0.f;
-          t[q] = ((p0 + p1) + p2) + p3;
-        }
+        if (q_used<WITH_XY, WITH_INV>(q))
+          t[q] = combine_waves<NU, ACC_STRIDE>(s_acc, q_slot<WITH_XY, WITH_INV>(q), tid, my_mask);
       }
       // the conic rows' factors o (-1/2, -1, -1/2) (see the hit loop)
       const float op = s_rp[2 * BATCH + tid].y;

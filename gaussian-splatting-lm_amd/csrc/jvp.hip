@@ -7,7 +7,11 @@
 //   k_render_matvec    the fused pair: JVP pass -> u = 2 w (.) J v in registers -> VJP pass ->
 //                      one reduced row per (tile, Gaussian); the per-pixel J v never touches HBM.
 //                      With the compact LM records the JVP pass runs one independent wave per quadrant
-//                      (jvp_wave_packed, no block barrier; k_render_jv_wave is the J v-only form).
+//                      (jvp_wave_packed, no block barrier; k_render_jv_wave is the J v-only form); with
+//                      screen-position tangents the block-cooperative jvp_tile.
+//   k_render_matvec_exposure   k_render_matvec<false> with the exposure map between its passes; the two share
+//                      one LDS plan (MatvecLds) and one set of per-pixel loads (MatvecPix).
+// Every kernel here starts with gslm_tile.hpp's tile_pix; jvp_tile takes its per-wave bounds from wave_bounds.
 #include "gslm_tile.hpp"
 #include "gslm_chain.hpp"
 
@@ -22,26 +26,25 @@ struct JvpPix {
 // Front-to-back tangent pass over the tile, BATCH list entries staged in LDS per round.
 // Block-uniform; blockDim = 256.  Wave w visits only the batch elements whose alpha region reaches its
 // 8x8 quadrant (publish_quad_masks) and that lie before the last position any of its pixels blends (the
-// primal's n_contrib; the same per-wave bound as vjp_tile); a lane blends entry `pos` only while
+// primal's n_contrib; wave_bounds, as vjp_tile); a lane blends entry `pos` only while
 // pos < its own n_contrib -- the stop decision frozen at the primal, without a per-iteration done flag.
+// Records: the primal's three float4 (the third as a float2) and the 12-float tangent record of the drop-in
+// JVP, [dx dy da db | dc dop dr dg | db dinv].  (The LM product's compact records go through jvp_wave_packed.)
 template <bool WITH_XY, bool WITH_INV, int BATCH>
-__device__ __forceinline__ void jvp_tile(JvpPix& o, bool inside, float pxf, float pyf, int tile_x, int tile_y,
-                                         uint32_t last, uint2 range, const uint32_t* __restrict__ point_list,
-                                         const float4* __restrict__ rec, const float4* __restrict__ trec,
+__device__ __forceinline__ void jvp_tile(JvpPix& o, bool inside, float pxf, float pyf, uint32_t last, uint2 range,
+                                         const uint32_t* __restrict__ point_list, const float4* __restrict__ rec,
+                                         const float4* __restrict__ trec,
                                          float4* s_r0, float4* s_r1, float2* s_r2, float4* s_t0, float4* s_t1,
                                          float2* s_t2, uint64_t* s_bits, int* s_cnt) {
-  constexpr bool PACKED = !WITH_XY && !WITH_INV;  // the LM product's records (see the staging below)
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  static_assert(WITH_XY || WITH_INV, "the LM product's compact records are jvp_wave_packed's");
+  const int tid = threadIdx.x, w = tid >> 6;
   o.T = 1.f;
   o.dT = 0.f;
   o.dC[0] = o.dC[1] = o.dC[2] = 0.f;
   o.dD = 0.f;
   const uint32_t my_last = inside ? last : 0u;
-  const int wmax = wave_max_u((int)my_last);
-  if (lane == 0) s_cnt[w] = wmax;
-  __syncthreads();
-  const int wm0 = s_cnt[0], wm1 = s_cnt[1], wm2 = s_cnt[2], wm3 = s_cnt[3];
-  const int n_eff = min(max(max(wm0, wm1), max(wm2, wm3)), (int)(range.y - range.x));
+  const WaveBounds wb = wave_bounds(my_last, range, s_cnt);
+  const int n_eff = wb.n_eff;
   const int rounds = (n_eff + BATCH - 1) / BATCH;
   for (int r = 0; r < rounds; ++r) {
     __syncthreads();  // the previous batch has been consumed
@@ -51,56 +54,21 @@ __device__ __forceinline__ void jvp_tile(JvpPix& o, bool inside, float pxf, floa
       const uint32_t e = point_list[range.x + k];
       const int64_t g = pl_id(e);
       // quadrants it can touch, and only the waves that still blend at this list position
-      m = pl_mask(e) & ((k < wm0 ? 1u : 0u) | (k < wm1 ? 2u : 0u) | (k < wm2 ? 4u : 0u) | (k < wm3 ? 8u : 0u));
+      m = pl_mask(e) & wb.blending(k);
       s_r0[tid] = rec[RECS * g + 0];
       s_r1[tid] = rec[RECS * g + 1];
       const float4 r2 = rec[RECS * g + 2];
-      if (PACKED) {
-        // the LM rows' compact tangent record (store_trec): [da db dc dop | dr dg db 0].  The product's 9 primal +
-        // 7 tangent floats as 4 float4 at one LDS stride: the hit loop reads them with one address register;
-        // the tangent conic carries its power factors (-1/2, -1, -1/2)
-        const float4 c0 = trec[2 * g + 0], c1 = trec[2 * g + 1];
-        s_t0[tid] = make_float4(r2.x, -0.5f * c0.x, -c0.y, -0.5f * c0.z);  // blue, da', db', dc'
-        s_t1[tid] = make_float4(c0.w, c1.x, c1.y, c1.z);                    // dopacity, dr, dg, db
-      } else {
-        const float4 t0 = trec[3 * g + 0], t1 = trec[3 * g + 1], t2 = trec[3 * g + 2];
-        s_r2[tid] = make_float2(r2.x, r2.y);
-        s_t0[tid] = t0;
-        s_t1[tid] = t1;
-        s_t2[tid] = make_float2(t2.x, t2.y);
-      }
+      const float4 t0 = trec[3 * g + 0], t1 = trec[3 * g + 1], t2 = trec[3 * g + 2];
+      s_r2[tid] = make_float2(r2.x, r2.y);
+      s_t0[tid] = t0;
+      s_t1[tid] = t1;
+      s_t2[tid] = make_float2(t2.x, t2.y);
     }
     publish_quad_masks(m, s_bits);
     __syncthreads();
     // this wave's hits in list order (latency is hidden by occupancy -- 8 waves per SIMD -- rather than
     // by register prefetch, which costs issue slots and occupancy)
     HitIter it(s_bits, w);
-    if constexpr (PACKED) {
-      for (int j = it.next(); j >= 0; j = it.next()) {
-        const float4 a = s_r0[j], b = s_r1[j], C = s_t0[j], D = s_t1[j];
-        asm volatile("" : : "v"(b.z), "v"(b.w), "v"(C.x), "v"(C.y), "v"(C.z), "v"(C.w), "v"(D.x), "v"(D.y), "v"(D.z),
-                     "v"(D.w));
-        const uint32_t pos = (uint32_t)(r * BATCH + j);
-        const float dx = a.x - pxf, dy = a.y - pyf;
-        const float power = gpower(a.z, a.w, b.x, dx, dy);
-        const float G = gexp(power);
-        const float alpha = fminf(0.99f, b.y * G);
-        if (pos < my_last && !(power > 0.0f) && alpha >= 1.0f / 255.0f) {
-#pragma clang fp contract(fast)
-          const float dpower = fmaf(dx, fmaf(C.y, dx, C.z * dy), C.w * dy * dy);  // 5 VALU, not 6
-          const float dalpha = G * (D.x + b.y * dpower);
-          const float wt = alpha * o.T;
-          const float dw = dalpha * o.T + alpha * o.dT;
-          // two FMAs into the accumulator per channel (not mul + fma + add)
-          o.dC[0] = fmaf(b.z, dw, fmaf(D.y, wt, o.dC[0]));
-          o.dC[1] = fmaf(b.w, dw, fmaf(D.z, wt, o.dC[1]));
-          o.dC[2] = fmaf(C.x, dw, fmaf(D.w, wt, o.dC[2]));
-          o.dT = o.dT * (1.f - alpha) - o.T * dalpha;
-          o.T = o.T * (1.f - alpha);
-        }
-      }
-      continue;
-    }
     for (int j = it.next(); j >= 0; j = it.next()) {
       const float4 a = s_r0[j], b = s_r1[j], t0 = s_t0[j], t1 = s_t1[j];
       const float2 cc = s_r2[j], t2 = s_t2[j];
@@ -138,7 +106,11 @@ __device__ __forceinline__ void jvp_tile(JvpPix& o, bool inside, float pxf, floa
 // Front-to-back tangent pass of ONE wave over its 8x8 quadrant q, independent of the tile's other waves (no
 // block barrier): 64 list positions per round, each lane fetches one; the entries whose quadrant mask holds q
 // stage the compact LM record in the wave's own LDS slots (lane-indexed), and the wave walks the round's hit
-// bits in list order.  Same per-lane arithmetic and decisions as jvp_tile's PACKED branch.
+// bits in list order.  The record: the primal's nine floats and the LM rows' compact tangent record (store_trec:
+// [da db dc dop | dr dg db 0]) as 4 float4 at one LDS stride -- [x y a b], [c o r g], [blue da' db' dc'],
+// [dop dr dg db] -- which the hit loop reads with one address register; the tangent conic carries its power
+// factors (da' = -da / 2, db' = -db, dc' = -dc / 2).  A lane blends position pos only while pos < its own n_contrib
+// (my_last): the skip and stop decisions are the primal's.
 __device__ __forceinline__ void jvp_wave_packed(JvpPix& o, float pxf, float pyf, uint32_t my_last, int wm, int q,
                                                 const uint32_t* __restrict__ pl, const float4* __restrict__ rec,
                                                 const float4* __restrict__ trec, float4* s) {
@@ -196,6 +168,18 @@ __device__ __forceinline__ void jvp_wave_packed(JvpPix& o, float pxf, float pyf,
   }
 }
 
+// jvp_wave_packed for the thread's wave on its own quadrant of tile p: the wave's bound (the largest n_contrib of its
+// pixels, `last` being 0 outside the image; clamped by the range length as wave_bounds' n_eff is) and its 256 float4
+// of the 4 x 256 at s_rec.
+__device__ __forceinline__ void jvp_wave_quadrant(JvpPix& o, const TilePix& p, uint32_t last, uint2 range,
+                                                  const uint32_t* __restrict__ point_list,
+                                                  const float4* __restrict__ rec, const float4* __restrict__ trec,
+                                                  float4* s_rec) {
+  const int q = threadIdx.x >> 6;
+  const int wm = __builtin_amdgcn_readfirstlane(min(wave_max_u((int)last), (int)(range.y - range.x)));
+  jvp_wave_packed(o, (float)p.px, (float)p.py, last, wm, q, point_list + range.x, rec, trec, s_rec + 256 * q);
+}
+
 // J v only, compact LM records, one independent wave per quadrant (jvp_wave_packed).
 __global__ __launch_bounds__(256) void k_render_jv_wave(ViewK v, const uint2* __restrict__ ranges,
                                                          const uint32_t* __restrict__ tile_order,
@@ -203,20 +187,13 @@ __global__ __launch_bounds__(256) void k_render_jv_wave(ViewK v, const uint2* __
                                                          const float4* __restrict__ rec, const float4* __restrict__ trec,
                                                          const uint32_t* __restrict__ n_contrib,
                                                          float* __restrict__ out_color_t) {
-  __shared__ float4 s_rec[4][4 * 64];
-  const int tile = (int)tile_order[blockIdx.x];
-  const int tile_x = tile % v.gx, tile_y = tile / v.gx;
-  const int tid = threadIdx.x, q = tid >> 6;
-  int px, py;
-  tile_pixel(tile_x, tile_y, tid, px, py);
-  const bool inside = px < v.W && py < v.H;
-  const int64_t pid = (int64_t)py * v.W + px;
-  const uint32_t last = inside ? n_contrib[pid] : 0u;
-  const uint2 range = ranges[tile];
-  const int wm = __builtin_amdgcn_readfirstlane(min(wave_max_u((int)last), (int)(range.y - range.x)));
+  __shared__ float4 s_rec[4 * 256];
+  const TilePix p = tile_pix(v, tile_order);
+  const int64_t pid = p.pid;
+  const uint32_t last = p.inside ? n_contrib[pid] : 0u;
   JvpPix o;
-  jvp_wave_packed(o, (float)px, (float)py, last, wm, q, point_list + range.x, rec, trec, s_rec[q]);
-  if (inside) {
+  jvp_wave_quadrant(o, p, last, ranges[p.tile], point_list, rec, trec, s_rec);
+  if (p.inside) {
     const int64_t HW = (int64_t)v.H * v.W;
     out_color_t[pid] = o.dC[0] + o.dT * v.bg[0];
     out_color_t[HW + pid] = o.dC[1] + o.dT * v.bg[1];
@@ -236,24 +213,67 @@ __global__ __launch_bounds__(256) void k_render_jvp(ViewK v, const uint2* __rest
   __shared__ float2 s_r2[B], s_t2[B];
   __shared__ uint64_t s_bits[16];
   __shared__ int s_cnt[4];
-  const int tile = (int)tile_order[blockIdx.x];
-  const int tile_x = tile % v.gx, tile_y = tile / v.gx;
-  const int tid = threadIdx.x;
-  int px, py;
-  tile_pixel(tile_x, tile_y, tid, px, py);
-  const bool inside = px < v.W && py < v.H;
-  const int64_t pid = (int64_t)py * v.W + px;
-  const uint32_t last = inside ? n_contrib[pid] : 0u;
+  const TilePix p = tile_pix(v, tile_order);
+  const int64_t pid = p.pid;
+  const uint32_t last = p.inside ? n_contrib[pid] : 0u;
   JvpPix o;
-  jvp_tile<WITH_XY, true, B>(o, inside, (float)px, (float)py, tile_x, tile_y, last, ranges[tile], point_list, rec,
-                                 trec, s_r0, s_r1, s_r2, s_t0, s_t1, s_t2, s_bits, s_cnt);
-  if (inside) {
+  jvp_tile<WITH_XY, true, B>(o, p.inside, (float)p.px, (float)p.py, last, ranges[p.tile], point_list, rec, trec, s_r0,
+                             s_r1, s_r2, s_t0, s_t1, s_t2, s_bits, s_cnt);
+  if (p.inside) {
     const int64_t HW = (int64_t)v.H * v.W;
     out_color_t[pid] = o.dC[0] + o.dT * v.bg[0];
     out_color_t[HW + pid] = o.dC[1] + o.dT * v.bg[1];
     out_color_t[2 * HW + pid] = o.dC[2] + o.dT * v.bg[2];
     if (out_inv_t) out_inv_t[pid] = o.dD;
   }
+}
+
+// The LDS plan of k_render_matvec<WITH_XY> (k_render_matvec_exposure uses <false>'s), in float4 of one region s.
+// The JVP pass's records and the VJP pass's staged records and per-wave partials (+ its n_eff scratch) are never
+// live together (vjp_tile starts with a block barrier).  Without screen-position tangents the JVP pass runs one
+// independent wave per quadrant (jvp_wave_quadrant: 4 x 256 float4 of wave-private records from s); with them the
+// block-cooperative jvp_tile, its primal records where vjp_tile's planes will be and its tangent records below.
+template <bool WITH_XY>
+struct MatvecLds {
+  static constexpr int B = MATVEC_BATCH;
+  // vjp_tile's partials, rounded up to 512 B: its record planes then start on a ds_read2st64 stride (no address add
+  // per visit)
+  static constexpr int kAcc = (vjp_acc_floats<WITH_XY, false, B>() + 3) / 4 + 31 & ~31;
+  static constexpr int kVjp = kAcc + B + B + B / 2;  // + vjp_tile's 5 float2 planes (jvp_tile's r0, r1, r2)
+  static constexpr int kJvp = WITH_XY ? 0 : 4 * 256;
+  static constexpr int kFloat4 = kVjp > kJvp ? kVjp : kJvp;
+  static_assert(!WITH_XY || kAcc >= 2 * B + B / 2, "jvp_tile's tangent records must fit below r0");
+  static __device__ __forceinline__ float* acc(float4* s) { return reinterpret_cast<float*>(s); }
+  static __device__ __forceinline__ int* misc(float4* s) { return reinterpret_cast<int*>(s); }  // before acc is written
+  static __device__ __forceinline__ float2* planes(float4* s) { return reinterpret_cast<float2*>(s + kAcc); }
+  static __device__ __forceinline__ float4* r0(float4* s) { return s + kAcc; }
+  static __device__ __forceinline__ float4* r1(float4* s) { return s + kAcc + B; }
+  static __device__ __forceinline__ float2* r2(float4* s) { return reinterpret_cast<float2*>(s + kAcc + 2 * B); }
+  static __device__ __forceinline__ float4* t0(float4* s) { return s; }
+  static __device__ __forceinline__ float4* t1(float4* s) { return s + B; }
+  static __device__ __forceinline__ float2* t2(float4* s) { return reinterpret_cast<float2*>(s + 2 * B); }
+};
+
+// A pixel's inputs to the fused product: the primal's n_contrib and final T and the three channel weights (zeros
+// outside the image).
+struct MatvecPix {
+  uint32_t last;
+  float Tf, w0, w1, w2;
+};
+__device__ __forceinline__ MatvecPix load_matvec_pix(const ViewK& v, const TilePix& p,
+                                                     const float* __restrict__ final_T,
+                                                     const uint32_t* __restrict__ n_contrib,
+                                                     const float* __restrict__ weight) {
+  MatvecPix m{0u, 0.f, 0.f, 0.f, 0.f};
+  if (p.inside) {
+    const int64_t HW = (int64_t)v.H * v.W;
+    m.last = n_contrib[p.pid];
+    m.Tf = final_T[p.pid];
+    m.w0 = weight[p.pid];
+    m.w1 = weight[HW + p.pid];
+    m.w2 = weight[2 * HW + p.pid];
+  }
+  return m;
 }
 
 // Fused (J^T W J) v for one view: JVP pass, per-pixel weight, VJP pass.
@@ -267,70 +287,35 @@ __global__ __launch_bounds__(256, WITH_XY ? 6 : 8) void k_render_matvec(ViewK v,
                                                         const uint32_t* __restrict__ goff,
                                                         const float* __restrict__ final_T,
                                                         const uint32_t* __restrict__ n_contrib,
-                                                        const float* __restrict__ weight, float4* __restrict__ contrib,
-                                                        int write_tail) {
+                                                        const float* __restrict__ weight, float4* __restrict__ contrib) {
   // 128-entry batches.  The LM instantiation (WITH_XY = false): 20.1 KB of LDS and 47 VGPRs -> 8 blocks per CU, 8
   // waves per SIMD (hipcc -Rpass-analysis=kernel-resource-usage; profiles/r04/resource_usage.txt); the drop-in
   // one (screen-position tangents): 23.8 KB, 64 VGPRs -> 6 blocks per CU
-  constexpr int B = MATVEC_BATCH;
+  using Lds = MatvecLds<WITH_XY>;
+  constexpr int B = Lds::B;
   __shared__ uint64_t s_bits[16];
   __shared__ int s_cnt[4];
-  // The JVP pass's records and the VJP pass's staged records, per-wave partials (+ its n_eff scratch) are never
-  // live together (vjp_tile starts with a block barrier): one LDS region.  Without screen-position tangents
-  // the JVP pass runs one independent wave per quadrant (jvp_wave_packed: 4 x 256 float4 of wave-private
-  // records); with them the block-cooperative jvp_tile.
-  // float4; rounded up to 512 B: vjp_tile's record planes then start on a ds_read2st64 stride (no address add per visit)
-  constexpr int kAcc = (vjp_acc_floats<WITH_XY, false, B>() + 3) / 4 + 31 & ~31;
-  constexpr int kVjp = kAcc + B + B + B / 2;  // + s_r0, s_r1, s_r2 (vjp_tile: 5 float2 planes)
-  constexpr int kJvp = WITH_XY ? 0 : 4 * 256;
-  static_assert(!WITH_XY || kAcc >= 2 * B + B / 2, "jvp_tile's tangent records must fit below s_r0");
-  __shared__ float4 s_lds[kVjp > kJvp ? kVjp : kJvp];
-  float* s_acc = reinterpret_cast<float*>(s_lds);
-  int* s_misc = reinterpret_cast<int*>(s_lds);
-  float4* s_r0 = s_lds + kAcc;
-  float4* s_r1 = s_r0 + B;
-  float2* s_r2 = reinterpret_cast<float2*>(s_r1 + B);
-  float4* s_t0 = s_lds;  // jvp_tile's tangent records (WITH_XY), below s_r0
-  float4* s_t1 = s_t0 + B;
-  float2* s_t2 = reinterpret_cast<float2*>(s_t1 + B);
+  __shared__ float4 s_lds[Lds::kFloat4];
   if (cg_stopped(v)) return;
-  const int tile = (int)tile_order[blockIdx.x];
-  const int tile_x = tile % v.gx, tile_y = tile / v.gx;
-  const int tid = threadIdx.x;
-  int px, py;
-  tile_pixel(tile_x, tile_y, tid, px, py);
-  const bool inside = px < v.W && py < v.H;
-  const int64_t pid = (int64_t)py * v.W + px;
-  const int64_t HW = (int64_t)v.H * v.W;
-  const uint2 range = ranges[tile];
-  uint32_t last = 0;
-  float Tf = 0.f, w0 = 0.f, w1 = 0.f, w2 = 0.f;
-  if (inside) {
-    last = n_contrib[pid];
-    Tf = final_T[pid];
-    w0 = weight[pid];
-    w1 = weight[HW + pid];
-    w2 = weight[2 * HW + pid];
-  }
+  const TilePix p = tile_pix(v, tile_order);
+  const uint2 range = ranges[p.tile];
+  const MatvecPix m = load_matvec_pix(v, p, final_T, n_contrib, weight);
   JvpPix o;
-  if constexpr (WITH_XY) {
-    jvp_tile<WITH_XY, false, B>(o, inside, (float)px, (float)py, tile_x, tile_y, last, range, point_list, rec, trec,
-                                s_r0, s_r1, s_r2, s_t0, s_t1, s_t2, s_bits, s_cnt);
-  } else {
-    const int q = tid >> 6;
-    const int wm = __builtin_amdgcn_readfirstlane(min(wave_max_u(inside ? (int)last : 0), (int)(range.y - range.x)));
-    jvp_wave_packed(o, (float)px, (float)py, inside ? last : 0u, wm, q, point_list + range.x, rec, trec,
-                    s_lds + 256 * q);
-  }
+  if constexpr (WITH_XY)
+    jvp_tile<WITH_XY, false, B>(o, p.inside, (float)p.px, (float)p.py, m.last, range, point_list, rec, trec,
+                                Lds::r0(s_lds), Lds::r1(s_lds), Lds::r2(s_lds), Lds::t0(s_lds), Lds::t1(s_lds),
+                                Lds::t2(s_lds), s_bits, s_cnt);
+  else
+    jvp_wave_quadrant(o, p, m.last, range, point_list, rec, trec, s_lds);
   // u = 2 * w (.) (J v)   -- factor 2: the [r; r] residual aliasing of batch_training_loss.py:17
-  const float u0 = 2.f * w0 * (o.dC[0] + o.dT * v.bg[0]);
-  const float u1 = 2.f * w1 * (o.dC[1] + o.dT * v.bg[1]);
-  const float u2 = 2.f * w2 * (o.dC[2] + o.dT * v.bg[2]);
+  const float u0 = 2.f * m.w0 * (o.dC[0] + o.dT * v.bg[0]);
+  const float u1 = 2.f * m.w1 * (o.dC[1] + o.dT * v.bg[1]);
+  const float u2 = 2.f * m.w2 * (o.dC[2] + o.dT * v.bg[2]);
   VjpPix st;
-  vjp_init(st, v, inside, Tf, last, u0, u1, u2, 0.f);
-  vjp_tile<WITH_XY, false, WITH_XY ? 3 : 2, B>(st, inside, (float)px, (float)py, tile_x, tile_y, range, point_list, rec,
-                                            slots, rect, goff, reinterpret_cast<float2*>(s_r0), s_bits, s_acc, s_misc, contrib,
-                                            write_tail != 0);
+  vjp_init(st, v, p.inside, m.Tf, m.last, u0, u1, u2, 0.f);
+  vjp_tile<WITH_XY, false, WITH_XY ? 3 : 2, B>(st, (float)p.px, (float)p.py, p.tile_x, p.tile_y, range, point_list, rec,
+                                               slots, rect, goff, Lds::planes(s_lds), s_bits, Lds::acc(s_lds),
+                                               Lds::misc(s_lds), contrib);
 }
 
 // k_render_matvec<false> under a trained per-camera exposure (GSLM_MV_EXPOSURE): between the two passes the
@@ -350,43 +335,20 @@ __global__ __launch_bounds__(256, 8) void k_render_matvec_exposure(
     const uint32_t* __restrict__ slots, const uint2* __restrict__ rect, const uint32_t* __restrict__ goff,
     const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib, const float* __restrict__ weight,
     float4* __restrict__ contrib, ExposureK ex) {
-  constexpr int B = MATVEC_BATCH;
+  using Lds = MatvecLds<false>;
   __shared__ uint64_t s_bits[16];
-  // the LDS plan of k_render_matvec<false>
-  constexpr int kAcc = (vjp_acc_floats<false, false, B>() + 3) / 4 + 31 & ~31;
-  constexpr int kVjp = kAcc + B + B + B / 2;
-  constexpr int kJvp = 4 * 256;
-  __shared__ float4 s_lds[kVjp > kJvp ? kVjp : kJvp];
-  float* s_acc = reinterpret_cast<float*>(s_lds);
-  int* s_misc = reinterpret_cast<int*>(s_lds);
-  float4* s_r0 = s_lds + kAcc;
+  __shared__ float4 s_lds[Lds::kFloat4];
   if (cg_stopped(v)) return;
-  const int tile = (int)tile_order[blockIdx.x];
-  const int tile_x = tile % v.gx, tile_y = tile / v.gx;
-  const int tid = threadIdx.x;
-  int px, py;
-  tile_pixel(tile_x, tile_y, tid, px, py);
-  const bool inside = px < v.W && py < v.H;
-  const int64_t pid = (int64_t)py * v.W + px;
+  const TilePix p = tile_pix(v, tile_order);
+  const int64_t pid = p.pid;
   const int64_t HW = (int64_t)v.H * v.W;
-  const uint2 range = ranges[tile];
-  uint32_t last = 0;
-  float Tf = 0.f, w0 = 0.f, w1 = 0.f, w2 = 0.f;
-  if (inside) {
-    last = n_contrib[pid];
-    Tf = final_T[pid];
-    w0 = weight[pid];
-    w1 = weight[HW + pid];
-    w2 = weight[2 * HW + pid];
-  }
+  const uint2 range = ranges[p.tile];
+  const MatvecPix m = load_matvec_pix(v, p, final_T, n_contrib, weight);
   JvpPix o;
-  const int q = tid >> 6;
-  const int wm = __builtin_amdgcn_readfirstlane(min(wave_max_u(inside ? (int)last : 0), (int)(range.y - range.x)));
-  jvp_wave_packed(o, (float)px, (float)py, inside ? last : 0u, wm, q, point_list + range.x, rec, trec,
-                  s_lds + 256 * q);
+  jvp_wave_quadrant(o, p, m.last, range, point_list, rec, trec, s_lds);
   // the forward's colour: loaded after the tangent pass (three registers it need not carry)
   float R0 = 0.f, R1 = 0.f, R2 = 0.f;
-  if (inside) {
+  if (p.inside) {
     R0 = ex.color[pid];
     R1 = ex.color[HW + pid];
     R2 = ex.color[2 * HW + pid];
@@ -400,10 +362,10 @@ __global__ __launch_bounds__(256, 8) void k_render_matvec_exposure(
   const float dC1 = ((dR0 * X[1] + dR1 * X[5]) + dR2 * X[9]) + (((R0 * V[1] + R1 * V[5]) + R2 * V[9]) + V[7]);
   const float dC2 = ((dR0 * X[2] + dR1 * X[6]) + dR2 * X[10]) + (((R0 * V[2] + R1 * V[6]) + R2 * V[10]) + V[11]);
   // u = 2 * w (.) dC   -- factor 2: the [r; r] residual aliasing of batch_training_loss.py:17
-  const float u0 = 2.f * w0 * dC0;
-  const float u1 = 2.f * w1 * dC1;
-  const float u2 = 2.f * w2 * dC2;
-  if (inside) {
+  const float u0 = 2.f * m.w0 * dC0;
+  const float u1 = 2.f * m.w1 * dC1;
+  const float u2 = 2.f * m.w2 * dC2;
+  if (p.inside) {
     ex.u[pid] = u0;
     ex.u[HW + pid] = u1;
     ex.u[2 * HW + pid] = u2;
@@ -412,9 +374,9 @@ __global__ __launch_bounds__(256, 8) void k_render_matvec_exposure(
   const float ub1 = (X[4] * u0 + X[5] * u1) + X[6] * u2;
   const float ub2 = (X[8] * u0 + X[9] * u1) + X[10] * u2;
   VjpPix st;
-  vjp_init(st, v, inside, Tf, last, ub0, ub1, ub2, 0.f);
-  vjp_tile<false, false, 2, B>(st, inside, (float)px, (float)py, tile_x, tile_y, range, point_list, rec, slots, rect,
-                               goff, reinterpret_cast<float2*>(s_r0), s_bits, s_acc, s_misc, contrib, false);
+  vjp_init(st, v, p.inside, m.Tf, m.last, ub0, ub1, ub2, 0.f);
+  vjp_tile<false, false, 2, Lds::B>(st, (float)p.px, (float)p.py, p.tile_x, p.tile_y, range, point_list, rec, slots,
+                                    rect, goff, Lds::planes(s_lds), s_bits, Lds::acc(s_lds), Lds::misc(s_lds), contrib);
 }
 
 // ------------------------------------------------------------------ launchers
@@ -459,12 +421,12 @@ int launch_matvec_render(const ViewK& v, const GaussK& t, const GeomBufs& gb, co
   }
   if (mask_xyz)
     hipLaunchKernelGGL(k_render_matvec<false>, dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges, bb.tile_order, bb.point_list,
-                       gb.rec, sb.trec, bb.slots, gb.rect, gb.goff, ib.final_T, ib.n_contrib, weight, sb.contrib,
-                       0);  // no tail rows: the row map holds head entries only
+                       gb.rec, sb.trec, bb.slots, gb.rect, gb.goff, ib.final_T, ib.n_contrib, weight,
+                       sb.contrib);
   else
     hipLaunchKernelGGL(k_render_matvec<true>, dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges, bb.tile_order, bb.point_list,
-                       gb.rec, sb.trec, bb.slots, gb.rect, gb.goff, ib.final_T, ib.n_contrib, weight, sb.contrib,
-                       0);  // no tail rows: the row map holds head entries only
+                       gb.rec, sb.trec, bb.slots, gb.rect, gb.goff, ib.final_T, ib.n_contrib, weight,
+                       sb.contrib);
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
 }

@@ -1,10 +1,11 @@
 // lm_diag.hip -- diag(J^T W J + D) of the LM normal equations on the LM rows (xyz frozen), and the vector kernels
 // of Jacobi-preconditioned CG.
 //
-//   k_render_diag    per tile, back to front over the list in the shape of vjp_tile's LM form (128-entry batches as
-//                    five float2 planes, quadrant-mask hit words, the per-wave n_contrib bounds): per head entry
-//                    twelve image sums over the pixels that blend it -- nine monomials sum w G^2 dx^i dy^j of the
-//                    geometry block and three colour sums -- one 48-byte row per entry through the LM row map.
+//   k_render_diag    per tile, back to front over the list with the parts of vjp_tile's pass (gslm_tile.hpp:
+//                    wave_bounds, stage_entry into 128-entry batches, primal_test, combine_waves) around a visit of
+//                    its own: per head entry twelve image sums over the pixels that blend it -- nine monomials
+//                    sum w G^2 dx^i dy^j of the geometry block and three colour sums -- one 48-byte row per entry
+//                    through the LM row map.
 //   k_gather_diag    per Gaussian: the sum of its head rows, the 4x4 block S in (conic a, b, c, effective opacity),
 //                    diag_j = c_j^T S c_j with c_j = chain_jvp of parameter j's unit tangent, and B_k^2 S_col[c]
 //                    for the SH groups; written into the flat layout (full or single-view projected), overwrite
@@ -33,24 +34,20 @@ __global__ __launch_bounds__(256) void k_render_diag(ViewK v, const uint2* __res
                                                      const uint32_t* __restrict__ n_contrib,
                                                      const float* __restrict__ weight, float4* __restrict__ rows) {
   constexpr int B = DIAG_BATCH;
-  constexpr int STR = B + 1;  // the 8 lanes storing one element's 8 slots hit 8 different banks
+  constexpr int STR = acc_stride<B>();
   __shared__ uint64_t s_bits[16];
   __shared__ int s_misc[4];
   __shared__ float s_acc[4 * ND * STR];  // [wave][value][batch element]
-  __shared__ float2 s_rp[5 * B];         // (x, y), (conic a, b), (conic c, opacity), (r, g), (b, 1/depth)
-  const int tile = (int)tile_order[blockIdx.x];
-  const int tile_x = tile % v.gx, tile_y = tile / v.gx;
+  __shared__ float2 s_rp[5 * B];         // the batch's five record planes (stage_entry)
+  const TilePix p = tile_pix(v, tile_order);
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  int px, py;
-  tile_pixel(tile_x, tile_y, tid, px, py);
-  const bool inside = px < v.W && py < v.H;
-  const int64_t pid = (int64_t)py * v.W + px;
+  const int64_t pid = p.pid;
   const int64_t HW = (int64_t)v.H * v.W;
-  const uint2 range = ranges[tile];
-  const float pxf = (float)px, pyf = (float)py;
+  const uint2 range = ranges[p.tile];
+  const float pxf = (float)p.px, pyf = (float)p.py;
   uint32_t last = 0;
   float T = 0.f, W0 = 0.f, W1 = 0.f, W2 = 0.f;
-  if (inside) {
+  if (p.inside) {
     last = n_contrib[pid];
     T = final_T[pid];
     // 2 w: the [r; r] pair, as in u = 2 w (.) J v
@@ -62,11 +59,8 @@ __global__ __launch_bounds__(256) void k_render_diag(ViewK v, const uint2* __res
   const float tb0 = -T * v.bg[0], tb1 = -T * v.bg[1], tb2 = -T * v.bg[2];
   // the colour accumulated behind the current entry, per channel (VjpPix::accd carries only its dot with the seed)
   float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;
-  const int wmax = wave_max_u((int)last);
-  if (lane == 0) s_misc[w] = wmax;
-  __syncthreads();
-  const int wm0 = s_misc[0], wm1 = s_misc[1], wm2 = s_misc[2], wm3 = s_misc[3];
-  const int n_eff = min(max(max(wm0, wm1), max(wm2, wm3)), (int)(range.y - range.x));
+  const WaveBounds wb = wave_bounds(last, range, s_misc);
+  const int n_eff = wb.n_eff;
   const int rounds = (n_eff + B - 1) / B;
   for (int r = 0; r < rounds; ++r) {
     const int base = n_eff - 1 - r * B;  // list position of batch element 0
@@ -74,18 +68,8 @@ __global__ __launch_bounds__(256) void k_render_diag(ViewK v, const uint2* __res
     __syncthreads();
     uint32_t my_slot = 0, my_mask = 0u;
     if (tid < cnt) {
-      const uint32_t e = point_list[range.x + base - tid];
-      const uint32_t g = pl_id(e);
-      my_mask = pl_mask(e);
-      const float4 r0 = rec[RECS * (int64_t)g + 0], r1 = rec[RECS * (int64_t)g + 1], r2 = rec[RECS * (int64_t)g + 2];
-      s_rp[tid] = make_float2(r0.x, r0.y);
-      s_rp[B + tid] = make_float2(r0.z, r0.w);
-      s_rp[2 * B + tid] = make_float2(r1.x, r1.y);
-      s_rp[3 * B + tid] = make_float2(r1.z, r1.w);
-      s_rp[4 * B + tid] = make_float2(r2.x, r2.y);
-      // only the waves that still blend at this list position
-      const int pos = base - tid;
-      my_mask &= (pos < wm0 ? 1u : 0u) | (pos < wm1 ? 2u : 0u) | (pos < wm2 ? 4u : 0u) | (pos < wm3 ? 8u : 0u);
+      uint32_t g;
+      my_mask = stage_entry<B>(point_list, range.x, base - tid, rec, wb, s_rp, tid, g);
       if (my_mask) my_slot = slots[range.x + base - tid];  // a head entry: it owns a row of the LM row map
     }
     publish_quad_masks(my_mask, s_bits);
@@ -97,36 +81,30 @@ __global__ __launch_bounds__(256) void k_render_diag(ViewK v, const uint2* __res
         const int hb = (int)__builtin_ctzll(hits);
         hits = clear_bit(hits, hb);
         const int j = 64 * wd + hb;
-        const float2 p0 = s_rp[j], p1 = s_rp[B + j], p2 = s_rp[2 * B + j], p3 = s_rp[3 * B + j];
-        const float2 c = s_rp[4 * B + j];
-        const uint32_t contributor = (uint32_t)(base - j);  // 0-based list position
-        // the primal tests round exactly as the forward's (and as k_render_matvec's): the same visits are blended
-        const float dx = p0.x - pxf, dy = p0.y - pyf;
-        const float power = gpower(p1.x, p1.y, p2.x, dx, dy);
-        const float G = gexp(power);
-        const float alpha = fminf(0.99f, p2.y * G);
-        const bool c_last = contributor < last, c_pow = !(power > 0.0f), c_alpha = alpha >= 1.0f / 255.0f;
-        const bool valid = c_last && c_pow && c_alpha;  // last = 0 outside the image
-        const bool any = (__builtin_amdgcn_ballot_w64(c_last) & __builtin_amdgcn_ballot_w64(c_pow) &
-                          __builtin_amdgcn_ballot_w64(c_alpha)) != 0ull;
+        const VisitRec e = load_visit<B>(s_rp, j);
+        const Primal pt = primal_test(e, pxf, pyf, (uint32_t)(base - j), last);  // base - j: 0-based list position
+        const float dx = pt.dx, dy = pt.dy;
         float r1v = 0.f, r2v = 0.f;
-        if (any) {
+        if (pt.any) {
           // an invalid lane runs the body with alpha = G = 0: its values are 0, T and the accumulation are unchanged
 #pragma clang fp contract(fast)
-          const float a_e = valid ? alpha : 0.f;
-          const float G_e = valid ? G : 0.f;
+          const float a_e = pt.valid ? pt.alpha : 0.f;
+          const float G_e = pt.valid ? pt.G : 0.f;
           const float inv1ma = rcp_f(1.f - a_e);
           T = T * inv1ma;  // the transmittance in front of this entry
           const float aT = a_e * T;
           const float aT2 = aT * aT;
           // g_c = d colour_c / d alpha = (col_c - acc_c) T - T_final bg_c / (1 - alpha): vjp_tile's dL_dalpha for
           // the seed e_c; this entry joins the accumulation behind the next one after it is used
-          const float d0 = p3.x - acc0, d1 = p3.y - acc1, d2 = c.x - acc2;
-          const float g0 = d0 * T + tb0 * inv1ma, g1 = d1 * T + tb1 * inv1ma, g2 = d2 * T + tb2 * inv1ma;
+          const float d0 = e.rg.x - acc0, d1 = e.rg.y - acc1, d2 = e.bd.x - acc2;
+          // (sums of two products name the product that is rounded: which one contraction would fuse is the
+          // compiler's choice, and it changes with the code around it)
+          const float g0 = fmaf(tb0, inv1ma, d0 * T), g1 = fmaf(tb1, inv1ma, d1 * T), g2 = fmaf(tb2, inv1ma, d2 * T);
           acc0 = acc0 + a_e * d0;
           acc1 = acc1 + a_e * d1;
           acc2 = acc2 + a_e * d2;
-          const float om = (W0 * g0 * g0 + W1 * g1 * g1) + W2 * g2 * g2;
+          // (W0 g0^2 + W1 g1^2) + W2 g2^2
+          const float om = fmaf(W2 * g2, g2, fmaf(W1 * g1, g1, W0 * g0 * g0));
           const float h = om * (G_e * G_e);
           const float dx2 = dx * dx, dxy = dx * dy, dy2 = dy * dy;
           const float hx2 = h * dx2, hxy = h * dxy, hy2 = h * dy2;
@@ -157,46 +135,16 @@ __global__ __launch_bounds__(256) void k_render_diag(ViewK v, const uint2* __res
       }
     }
     __syncthreads();
-    // rows only for the entries some wave visited; the four waves' partials in fixed quadrant order
+    // rows only for the entries some wave visited
     if (tid < cnt && my_mask) {
       float t[ND];
 #pragma unroll
-      for (int q = 0; q < ND; ++q) {
-        const float a0 = s_acc[(0 * ND + q) * STR + tid], a1 = s_acc[(1 * ND + q) * STR + tid];
-        const float a2 = s_acc[(2 * ND + q) * STR + tid], a3 = s_acc[(3 * ND + q) * STR + tid];
-        const float q0 = (my_mask & 1u) ? a0 : 0.f;
-        const float q1 = (my_mask & 2u) ? a1 : 0.f;
-        const float q2 = (my_mask & 4u) ? a2 : 0.f;
-        const float q3 = (my_mask & 8u) ? a3 : 0.f;
-        t[q] = ((q0 + q1) + q2) + q3;
-      }
+      for (int q = 0; q < ND; ++q) t[q] = combine_waves<ND, STR>(s_acc, q, tid, my_mask);
       rows[3 * (size_t)my_slot + 0] = make_float4(t[0], t[1], t[2], t[3]);
       rows[3 * (size_t)my_slot + 1] = make_float4(t[4], t[5], t[6], t[7]);
       rows[3 * (size_t)my_slot + 2] = make_float4(t[8], t[9], t[10], t[11]);
     }
   }
-}
-
-// block_sum_rows<3> on twelve-float rows (load_row<3> reads ten): the same chunks, loads and order of additions.
-__device__ __forceinline__ void block_sum_rows12(const float4* __restrict__ rows, uint32_t R0, uint32_t R1,
-                                                 uint32_t my_off, uint32_t my_n, float4* s_buf, float S[ND]) {
-#pragma unroll
-  for (int q = 0; q < ND; ++q) S[q] = 0.f;
-  const uint32_t my_end = my_off + my_n;
-  for (uint32_t c0 = R0; c0 < R1; c0 += GATHER_CHUNK) {
-    const uint32_t cn = min((uint32_t)GATHER_CHUNK, R1 - c0);
-    __syncthreads();  // the previous chunk has been consumed
-    for (uint32_t e = threadIdx.x; e < cn * 3; e += blockDim.x) s_buf[e] = rows[(size_t)c0 * 3 + e];
-    __syncthreads();
-    const uint32_t lo = max(my_off, c0), hi = min(my_end, c0 + cn);
-    for (uint32_t r = lo; r < hi; ++r) {
-      const float4 a = s_buf[3 * (r - c0) + 0], b = s_buf[3 * (r - c0) + 1], c = s_buf[3 * (r - c0) + 2];
-      S[0] += a.x; S[1] += a.y; S[2] += a.z; S[3] += a.w;
-      S[4] += b.x; S[5] += b.y; S[6] += b.z; S[7] += b.w;
-      S[8] += c.x; S[9] += c.y; S[10] += c.z; S[11] += c.w;
-    }
-  }
-  __syncthreads();  // s_buf may be reused by the caller
 }
 
 struct DiagK {
@@ -246,7 +194,7 @@ __global__ __launch_bounds__(256) void k_gather_diag(ViewK v, GaussK g, const ui
     const uint32_t n = valid ? tiles[i] : 0u;
     const uint32_t R0 = hscan[goff[i0]], R1 = hscan[goff[il] + tiles[il]];
     const uint32_t h0 = valid ? hscan[goff[i]] : R1, h1 = valid ? hscan[goff[i] + n] : R1;
-    block_sum_rows12(rows, R0, R1, h0, h1 - h0, s_buf, m);
+    block_sum_rows<3, ND>(rows, R0, R1, h0, h1 - h0, s_buf, m);
     seen = h1 > h0;
   }
   const int nc = (v.D + 1) * (v.D + 1);
