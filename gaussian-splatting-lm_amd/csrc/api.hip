@@ -810,6 +810,11 @@ static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gs
   int st = bind_all(view, gi, geom, binning, N, image, scratch, scratch_bytes, &b);
   if (st) return st;
   if (!vin || !y || !pixel_weight) { set_error("matvec: NULL argument"); return GSLM_ERR_INVALID; }
+  // (one extension struct lies behind the base: refused before either flag's extension is read)
+  if (opts && (opts->flags & GSLM_MV_DAMP_VEC) && (opts->flags & (GSLM_MV_LEAN | GSLM_MV_EXPOSURE))) {
+    set_error("matvec: GSLM_MV_DAMP_VEC excludes GSLM_MV_LEAN and GSLM_MV_EXPOSURE");
+    return GSLM_ERR_INVALID;
+  }
   // GSLM_MV_LEAN: opts is the base of a gslm_matvec_opts_lean; <v, y> may stay as the gather's partials (dot_defer)
   const gslm_cg_lean* lean = (opts && (opts->flags & GSLM_MV_LEAN))
                                  ? &reinterpret_cast<const gslm_matvec_opts_lean*>(opts)->lean : nullptr;
@@ -837,6 +842,28 @@ static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gs
     }
   }
   const double* damp7 = opts ? opts->damp7 : nullptr;
+  // GSLM_MV_DAMP_VEC: opts is the base of a gslm_matvec_opts_damp; GATHER adds d (.) v with d read per element
+  // (checked before anything is launched)
+  GradK dvec{};
+  const bool use_dvec = opts && (opts->flags & GSLM_MV_DAMP_VEC);
+  if (use_dvec) {
+    const gslm_grads* d = reinterpret_cast<const gslm_matvec_opts_damp*>(opts)->damp_vec;
+    if (damp7 || lean || expo || !mask_xyz || opts->pixel_seed || opts->jv_out || (stages & GSLM_STAGE_SCREEN) ||
+        opts->trec_in || opts->rest_basis) {
+      set_error("matvec: GSLM_MV_DAMP_VEC needs mask_xyz and excludes damp7, pixel_seed, jv_out, the SCREEN stage, "
+                "trec_in, rest_basis, GSLM_MV_LEAN and GSLM_MV_EXPOSURE");
+      return GSLM_ERR_INVALID;
+    }
+    if (!d || !d->means3D || !d->sh_dc || (b.g.M > 1 && !d->sh_rest) || !d->scales || !d->rotations || !d->opacities) {
+      set_error("matvec: GSLM_MV_DAMP_VEC with a NULL damp_vec or a NULL group of it");
+      return GSLM_ERR_INVALID;
+    }
+    if (d->sh_dc_stride != y->sh_dc_stride || (b.g.M > 1 && d->sh_rest_stride != y->sh_rest_stride)) {
+      set_error("matvec: GSLM_MV_DAMP_VEC: damp_vec has the groups and strides of v and y");
+      return GSLM_ERR_INVALID;
+    }
+    dvec = make_gradk(d);
+  }
   double* dot_out = opts ? opts->dot_vy : nullptr;
   const bool active = na >= 0;
   const int64_t rows = active ? na : b.g.P;  // rows of every group of vin and y
@@ -970,7 +997,7 @@ static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gs
   double* part = (dot_out || dot_defer) ? (double*)opts->dot_scratch : nullptr;
   if ((st = launch_gather_lm(b.v, gp, b.gb, b.sb, make_gradk(y), make_gradk(vin), damp7,
                              (stages & GSLM_STAGE_OVERWRITE) != 0, mask_xyz != 0, part, s, proj, ids, na, hrow,
-                             clamp_list)))
+                             clamp_list, use_dvec ? &dvec : nullptr)))
     return st;
   if (dot_out) return gslm_dot_finalize(part, (int32_t)((rows + 255) / 256), dot_out, stream);
   return GSLM_OK;
@@ -1297,6 +1324,10 @@ int gslm_gather_screen(const gslm_view* views, int32_t nviews, const gslm_gaussi
     set_error("gather_screen: NULL argument or nviews outside 1..16");
     return GSLM_ERR_INVALID;
   }
+  if (opts && (opts->flags & GSLM_MV_DAMP_VEC)) {
+    set_error("gather_screen: GSLM_MV_DAMP_VEC is an option of gslm_matvec_view_ex / gslm_matvec_view_active");
+    return GSLM_ERR_INVALID;
+  }
   ViewK vk[16];
   GaussK g;
   int st;
@@ -1334,6 +1365,10 @@ static int gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t 
   const bool active = na >= 0;
   if (!views || !ws || nviews < 1 || nviews > MAX_SCREEN_VIEWS || !gi || !vin || !y) {
     set_error("gather_views: NULL argument or nviews outside 1..16");
+    return GSLM_ERR_INVALID;
+  }
+  if (opts && (opts->flags & GSLM_MV_DAMP_VEC)) {
+    set_error("gather_views: GSLM_MV_DAMP_VEC is an option of gslm_matvec_view_ex / gslm_matvec_view_active");
     return GSLM_ERR_INVALID;
   }
   if (active && (na > gi->P || !hrow || hstride < na + 1 || fstride < na || (na > 0 && (!ids || !aflags)))) {

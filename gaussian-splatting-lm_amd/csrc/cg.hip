@@ -219,6 +219,18 @@ __global__ __launch_bounds__(256) void k_damp_add(int64_t n, const float* __rest
     y[i] = y[i] + (float)group_w(g, i) * x[i];
 }
 
+// Marquardt scaling: d = lambda[group] max(diag, floor).  The max is written as a select so that a NaN diagonal
+// stays NaN (fmaxf would return the floor and hide it from the solve's non-finite checks).  d may be diag.
+__global__ __launch_bounds__(256) void k_marquardt_scale(int64_t n, const float* diag, Groups g, float floor_,
+                                                         float* d) {
+  const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const float a = diag[i];
+    const float m = a < floor_ ? floor_ : a;
+    d[i] = (float)group_w(g, i) * m;
+  }
+}
+
 static int make_groups(const int64_t* bounds, const double* damp, int ng, Groups* g) {
   if (ng < 0 || ng > MAXG) {
     set_error("at most 8 damping groups");
@@ -359,6 +371,23 @@ int gslm_damp_add(int64_t n, const float* x, const int64_t* group_bounds, const 
   if (st) return st;
   if (n <= 0) return GSLM_OK;
   hipLaunchKernelGGL(k_damp_add, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, n, x, g, y);
+  GSLM_LAUNCH_CHECK();
+  return GSLM_OK;
+}
+
+int gslm_marquardt_scale(int64_t n, const float* diag, const int64_t* group_bounds, const double* group_lambda,
+                         int32_t ngroups, double floor, float* d, void* stream) {
+  Groups g;
+  int st = make_groups(group_bounds, group_lambda, ngroups, &g);
+  if (st) return st;
+  if (n < 0 || !(floor >= 0.0) || !(floor <= 3.0e38) || (n > 0 && (!diag || !d)) ||
+      (ngroups > 0 && (!group_bounds || !group_lambda))) {
+    set_error("gslm_marquardt_scale: negative n, a floor that is negative or not a finite float, or a NULL array");
+    return GSLM_ERR_INVALID;
+  }
+  if (n == 0) return GSLM_OK;
+  hipLaunchKernelGGL(k_marquardt_scale, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, n, diag, g, (float)floor,
+                     d);
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
 }

@@ -12,6 +12,7 @@
 #include "gslm_tile.hpp"
 #include "gslm_chain.hpp"
 #include "gslm_gather.hpp"
+#include <type_traits>
 
 namespace gslm {
 
@@ -119,7 +120,9 @@ __global__ __launch_bounds__(256) void k_preprocess_bwd(ViewK v, GaussK g, const
 // count) and row j of v and y, which hold the na listed Gaussians only.  The head rows of a block's 256 consecutive
 // listed Gaussians are still one contiguous range -- the Gaussians between them own none -- so the row sums and
 // their order are those of the full-layout kernel; their offsets come from the list's own hrow, read coalesced.
-template <bool WANT_MEANS, int ROWF4, bool PROJ, bool ACTIVE = false>
+// DVEC (GSLM_MV_DAMP_VEC): D v with d read per element from dk (lm_epilogue); the other instantiations take an empty
+// struct there and keep their code.
+template <bool WANT_MEANS, int ROWF4, bool PROJ, bool ACTIVE = false, bool DVEC = false>
 __global__ __launch_bounds__(256, PROJ ? 5 : 1) void k_gather_lm(ViewK v, GaussK g, const uint32_t* __restrict__ clampw,
                                                     const uint32_t* __restrict__ tiles,
                                                     const uint32_t* __restrict__ goff,
@@ -127,7 +130,8 @@ __global__ __launch_bounds__(256, PROJ ? 5 : 1) void k_gather_lm(ViewK v, GaussK
                                                     const float4* __restrict__ rows, FlatK o,
                                                     const int32_t* __restrict__ ids, int64_t na,
                                                     const uint32_t* __restrict__ hrow,
-                                                    const uint32_t* __restrict__ clamp_list) {
+                                                    const uint32_t* __restrict__ clamp_list,
+                                                    std::conditional_t<DVEC, DampVecK, NoDampVec> dk) {
   o.rest_proj = PROJ ? 1 : 0;  // the launcher picked the variant from it
   if (cg_stopped(v)) return;
   extern __shared__ __attribute__((aligned(16))) float s_rest[];  // row chunks, then the factored SH stage
@@ -159,7 +163,8 @@ __global__ __launch_bounds__(256, PROJ ? 5 : 1) void k_gather_lm(ViewK v, GaussK
   const bool listed = ACTIVE && clamp_list != nullptr;
   if (valid) chain_vjp<true>(v, g, listed ? j : i, n != 0, n ? (listed ? clamp_list[j] : clampw[i]) : 0u, G2, WANT_MEANS, co);
   if (ACTIVE) g.P = na;  // the epilogue writes rows j < na of y (it reads P and M of g only)
-  lm_epilogue<WANT_MEANS, true>((v.D + 1) * (v.D + 1), g, co, o, s_rest, s_dot);
+  if constexpr (DVEC) lm_epilogue<WANT_MEANS, true, true>((v.D + 1) * (v.D + 1), g, co, o, s_rest, s_dot, &dk);
+  else lm_epilogue<WANT_MEANS, true>((v.D + 1) * (v.D + 1), g, co, o, s_rest, s_dot);
 }
 
 // The SH-rest group of one view's Krylov space (GSLM_MV_SH_REST_PROJECTED): with one view every
@@ -252,7 +257,7 @@ int launch_preprocess_bwd(const ViewK& v, const GaussK& g, const GeomBufs& gb, c
 int launch_gather_lm(const ViewK& v, const GaussK& g, const GeomBufs& gb, const ScratchBufs& sb, const GradK& y,
                      const GradK& vin, const double* damp7, bool overwrite, bool mask_xyz, double* dot_part,
                      hipStream_t s, bool rest_proj, const int32_t* ids, int64_t na, const uint32_t* hrow,
-                     const uint32_t* clamp_list) {
+                     const uint32_t* clamp_list, const GradK* damp_vec) {
   const bool active = na >= 0;
   const int64_t nrows = active ? na : g.P;
   if (nrows == 0) return GSLM_OK;
@@ -267,24 +272,51 @@ int launch_gather_lm(const ViewK& v, const GaussK& g, const GeomBufs& gb, const 
   const size_t rest_lds = sh_stage_floats<true>(g.M) * sizeof(float);
   const size_t chunk_lds = (size_t)GATHER_CHUNK * (mask_xyz ? 2 : 3) * sizeof(float4);
   const size_t lds = (rest_lds > chunk_lds ? rest_lds : chunk_lds) + 16;
+  if (damp_vec) {
+    // the caller (matvec_view) has checked the groups and strides of d against v's and y's
+    const GradK& d = *damp_vec;
+    const DampVecK dk{{d.means3D, d.dc, d.rest, d.scales, d.rot, d.opac}};
+    bool ok = mask_xyz && !damp7;
+    for (int k = 0; k < 6; ++k)
+      if (!(k == 2 && g.M == 1) && (!o.v[k] || !dk.d[k])) ok = false;
+    if (!ok) {
+      set_error("internal: the damping vector runs on the LM rows with every group of v and d, without damp7");
+      return GSLM_ERR_INVALID;
+    }
+    o.use_damp = 1;
+    if (active && o.rest_proj)
+      hipLaunchKernelGGL((k_gather_lm<false, 2, true, true, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw,
+                         gb.tiles, gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow, clamp_list, dk);
+    else if (active)
+      hipLaunchKernelGGL((k_gather_lm<false, 2, false, true, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw,
+                         gb.tiles, gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow, clamp_list, dk);
+    else if (o.rest_proj)
+      hipLaunchKernelGGL((k_gather_lm<false, 2, true, false, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw,
+                         gb.tiles, gb.goff, sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr, dk);
+    else
+      hipLaunchKernelGGL((k_gather_lm<false, 2, false, false, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw,
+                         gb.tiles, gb.goff, sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr, dk);
+    GSLM_LAUNCH_CHECK();
+    return GSLM_OK;
+  }
   if (active && o.rest_proj)
     hipLaunchKernelGGL((k_gather_lm<false, 2, true, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles,
-                       gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow, clamp_list);
+                       gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow, clamp_list, NoDampVec{});
   else if (active)
     hipLaunchKernelGGL((k_gather_lm<false, 2, false, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles,
-                       gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow, clamp_list);
+                       gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow, clamp_list, NoDampVec{});
   else if (mask_xyz && o.rest_proj)
     hipLaunchKernelGGL((k_gather_lm<false, 2, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr);
+                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr, NoDampVec{});
   else if (mask_xyz)
     hipLaunchKernelGGL((k_gather_lm<false, 2, false>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr);
+                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr, NoDampVec{});
   else if (o.rest_proj)
     hipLaunchKernelGGL((k_gather_lm<true, 3, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr);
+                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr, NoDampVec{});
   else
     hipLaunchKernelGGL((k_gather_lm<true, 3, false>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr);
+                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr, NoDampVec{});
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
 }

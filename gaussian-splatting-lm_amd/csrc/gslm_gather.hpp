@@ -18,6 +18,13 @@ struct FlatK {
   double* dot_part;   // per-block partials of <v, y> over the written elements (NULL = off)
 };
 
+// GSLM_MV_DAMP_VEC: the damping as a vector, D = diag(d), in the groups and strides of v and y -- an argument of
+// its own (DVEC kernels only), so FlatK and the code of every other instantiation stay as they are
+struct DampVecK {
+  const float* d[6];  // xyz, dc, rest, scaling, rotation, opacity groups of d
+};
+struct NoDampVec {};
+
 // Block-cooperative version of sum_rows for the 256 consecutive Gaussians of a block: their rows are
 // one contiguous range (row_slot groups rows by Gaussian index), streamed through LDS in chunks of
 // GATHER_CHUNK rows with coalesced float4 loads; each thread then adds its own rows from LDS, in the
@@ -56,18 +63,28 @@ __device__ __forceinline__ void load_group(const float* v, const float* y, int64
   }
 }
 
+template <int K>
+__device__ __forceinline__ void load_damp(const float* d, int64_t base, bool on, float out[K]) {
+#pragma unroll
+  for (int k = 0; k < K; ++k) out[k] = on ? d[base + k] : 0.f;
+}
+
 // y = (overwrite ? 0 : y_old) + val + d v; returns sum of v * y_new (0 when dot is off).  y is stored nontemporal:
 // the gather's output is not re-read before the next kernel boundary writes the L2s back; measured -7 us on the
 // gather and -2.7 us per CG iteration (4 of 4 alternations; nontemporal gradient rows, which the gather reads at
 // once, cost +20 us: profiles/r06/ab_nontemporal_stores/)
-template <int K>
+// DVEC: d is per element (dvec[k]); the translation unit is compiled with -ffp-contract=off and nothing here opts back
+// in, so val + dvec[k] v is a multiply and an add, rounded as the scalar form's val + d v.
+template <int K, bool DVEC = false>
 __device__ __forceinline__ double store_group(float* y, float d, int use_damp, int64_t base, int overwrite, bool dot,
-                                              const float val[K], const float vin[K], const float yold[K]) {
+                                              const float val[K], const float vin[K], const float yold[K],
+                                              const float* dvec = nullptr) {
   double acc = 0.0;
 #pragma unroll
   for (int k = 0; k < K; ++k) {
     float x = val[k];
-    if (use_damp) x += d * vin[k];
+    if (DVEC) x += dvec[k] * vin[k];
+    else if (use_damp) x += d * vin[k];
     const float out = overwrite ? x : yold[k] + x;
     __builtin_nontemporal_store(out, &y[base + k]);  // streamed (profiles/r06/ab_nontemporal_stores/)
     if (dot) acc += (double)vin[k] * (double)out;
@@ -125,9 +142,11 @@ __host__ __device__ constexpr size_t sh_stage_floats(int M) {
 // Writes one block's 256 Gaussians' share of y (groups xyz, dc, rest, scaling, rotation, opacity)
 // from their ChainOut: y = (overwrite ? 0 : y) + J^T... + d v, and the block's partial of <v, y>.
 // Called by all 256 threads; co is ignored for threads past P.  s_rest: sh_stage_floats<FACTORED>(M).
-template <bool WANT_MEANS, bool FACTORED = false>
+// DVEC (GSLM_MV_DAMP_VEC): d is read per element from dk, in the load phase with v and y_old (17 more floats per
+// Gaussian, and one more stream beside v's in the SH-rest loop); o.damp is not used.
+template <bool WANT_MEANS, bool FACTORED = false, bool DVEC = false>
 __device__ __forceinline__ void lm_epilogue(int nc, const GaussK& g, const ChainOut& co, const FlatK& o, float* s_rest,
-                                            double* s_dot) {
+                                            double* s_dot, const DampVecK* dk = nullptr) {
   const int tid = threadIdx.x;
   const int64_t i0 = (int64_t)blockIdx.x * blockDim.x;
   const int64_t i = i0 + tid;
@@ -135,7 +154,7 @@ __device__ __forceinline__ void lm_epilogue(int nc, const GaussK& g, const Chain
   // a projected SH-rest group is a 3-wide group of its own below; the LDS-staged stream covers none
   const int R = o.rest_proj ? 0 : o.rest_V ? 3 * o.rest_V : 3 * (g.M - 1);
   const bool dot = o.dot_part != nullptr;
-  const int u = o.use_damp, ow = o.overwrite;
+  const int u = DVEC ? 1 : o.use_damp, ow = o.overwrite;
   const bool need_v = u || dot;
   double dacc = 0.0;
   __syncthreads();  // s_rest may still hold the caller's row chunks
@@ -149,25 +168,34 @@ __device__ __forceinline__ void lm_epilogue(int nc, const GaussK& g, const Chain
     load_group<3>(o.v[3], o.y[3], 3 * i, need_v, !ow, vs, ys);
     load_group<4>(o.v[4], o.y[4], 4 * i, need_v, !ow, vr, yr);
     load_group<1>(o.v[5], o.y[5], i, need_v, !ow, vo, yo);
+    float dx[3], ddc[3], ds[3], dr[4], dd[1];
+    if (DVEC) {
+      load_damp<3>(dk->d[0], 3 * i, xyz_on, dx);
+      load_damp<3>(dk->d[1], 3 * i, true, ddc);
+      load_damp<3>(dk->d[3], 3 * i, true, ds);
+      load_damp<4>(dk->d[4], 4 * i, true, dr);
+      load_damp<1>(dk->d[5], i, true, dd);
+    }
     if (WANT_MEANS) {
-      dacc += store_group<3>(o.y[0], o.damp[0], u, 3 * i, ow, dot, co.dmean, vx, yx);
+      dacc += store_group<3, DVEC>(o.y[0], o.damp[0], u, 3 * i, ow, dot, co.dmean, vx, yx, dx);
     } else if (ow) {
       const float z[3] = {0.f, 0.f, 0.f};
-      dacc += store_group<3>(o.y[0], o.damp[0], u, 3 * i, 1, dot && u, z, vx, yx);
+      dacc += store_group<3, DVEC>(o.y[0], o.damp[0], u, 3 * i, 1, dot && u, z, vx, yx, dx);
     }
-    dacc += store_group<3>(o.y[1], o.damp[1], u, 3 * i, ow, dot, co.dsh[0], vdc, ydc);
-    dacc += store_group<3>(o.y[3], o.damp[3], u, 3 * i, ow, dot, co.dscale, vs, ys);
-    dacc += store_group<4>(o.y[4], o.damp[4], u, 4 * i, ow, dot, co.drot, vr, yr);
+    dacc += store_group<3, DVEC>(o.y[1], o.damp[1], u, 3 * i, ow, dot, co.dsh[0], vdc, ydc, ddc);
+    dacc += store_group<3, DVEC>(o.y[3], o.damp[3], u, 3 * i, ow, dot, co.dscale, vs, ys, ds);
+    dacc += store_group<4, DVEC>(o.y[4], o.damp[4], u, 4 * i, ow, dot, co.drot, vr, yr, dr);
     const float dop[1] = {co.dop};
-    dacc += store_group<1>(o.y[5], o.damp[5], u, i, ow, dot, dop, vo, yo);
+    dacc += store_group<1, DVEC>(o.y[5], o.damp[5], u, i, ow, dot, dop, vo, yo, dd);
     if (o.rest_proj) {
       // B_rest (x) dres in the coordinate along B_rest / |B_rest|: |B_rest| dres
-      float vp[3], yp[3], val[3];
+      float vp[3], yp[3], val[3], dp[3];
       load_group<3>(o.v[2], o.y[2], 3 * i, need_v, !ow, vp, yp);
+      if (DVEC) load_damp<3>(dk->d[2], 3 * i, true, dp);
       const float nb = sh_rest_norm(co.shB, nc);
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) val[ch] = nb * co.dres[ch];
-      dacc += store_group<3>(o.y[2], o.damp[2], u, 3 * i, ow, dot, val, vp, yp);
+      dacc += store_group<3, DVEC>(o.y[2], o.damp[2], u, 3 * i, ow, dot, val, vp, yp, dp);
     } else if (o.rest_V) {
       // SH-rest coordinates: dsh[1 + j] holds coordinate j's gradient (k_gather_screen<true>)
 #pragma unroll
@@ -198,13 +226,14 @@ __device__ __forceinline__ void lm_epilogue(int nc, const GaussK& g, const Chain
   const float invR = R ? 1.0f / (float)R : 0.f;
   constexpr int U = 8;
   for (int64_t e0 = 0; e0 < total; e0 += (int64_t)U * blockDim.x) {
-    float vin[U], yold[U];
+    float vin[U], yold[U], dvin[U];
 #pragma unroll
     for (int k = 0; k < U; ++k) {
       const int64_t e = e0 + (int64_t)k * blockDim.x + tid;
       const bool in = e < total;
       vin[k] = (in && need_v) ? o.v[2][base + e] : 0.f;
       yold[k] = (in && !ow) ? o.y[2][base + e] : 0.f;
+      if (DVEC) dvin[k] = in ? dk->d[2][base + e] : 0.f;
     }
 #pragma unroll
     for (int k = 0; k < U; ++k) {
@@ -221,7 +250,8 @@ __device__ __forceinline__ void lm_epilogue(int nc, const GaussK& g, const Chain
         } else {
           val = s_rest[e];
         }
-        if (u) val += o.damp[2] * vin[k];
+        if (DVEC) val += dvin[k] * vin[k];
+        else if (u) val += o.damp[2] * vin[k];
         const float out = ow ? val : yold[k] + val;
         __builtin_nontemporal_store(out, &o.y[2][base + e]);
         if (dot) dacc += (double)vin[k] * (double)out;

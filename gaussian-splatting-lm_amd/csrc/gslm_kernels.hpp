@@ -663,7 +663,8 @@ int launch_exposure_rows(int H, int W, const float* color, const float* u, const
 int launch_gather_lm(const ViewK& v, const GaussK& g, const GeomBufs& gb, const ScratchBufs& sb, const GradK& y,
                      const GradK& vin, const double* damp7, bool overwrite, bool mask_xyz, double* dot_part,
                      hipStream_t s, bool rest_proj = false, const int32_t* ids = nullptr, int64_t na = -1,
-                     const uint32_t* hrow = nullptr, const uint32_t* clamp_list = nullptr);
+                     const uint32_t* hrow = nullptr, const uint32_t* clamp_list = nullptr,
+                     const GradK* damp_vec = nullptr);
 // the list-order copy of what the chains load per Gaussian (gslm_active_params) and the inverse map pos [P]
 // (pos[ids[j]] = j, -1 off the list)
 int launch_active_params(const float* means3D, const float* scales, const float* rot, const float* opac,

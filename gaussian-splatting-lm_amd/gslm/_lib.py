@@ -95,6 +95,11 @@ class GslmMatvecOptsExposure(ctypes.Structure):
     _fields_ = [("base", GslmMatvecOpts), ("exposure", GslmExposureOpts)]
 
 
+class GslmMatvecOptsDamp(ctypes.Structure):
+    """gslm_matvec_opts_damp: the product's options with GSLM_MV_DAMP_VEC set in base.flags."""
+    _fields_ = [("base", GslmMatvecOpts), ("damp_vec", ctypes.c_void_p)]
+
+
 class GslmViewWs(ctypes.Structure):
     """gslm_view_ws: one view's workspaces for gslm_gather_views."""
     _fields_ = [
@@ -297,6 +302,9 @@ EXPORTS = {
     "gslm_damp_add": (ctypes.c_int, [ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
                                      ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.c_void_p,
                                      ctypes.c_void_p]),
+    "gslm_marquardt_scale": (ctypes.c_int, [ctypes.c_int64, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64),
+                                            ctypes.POINTER(ctypes.c_double), ctypes.c_int32, ctypes.c_double,
+                                            ctypes.c_void_p, ctypes.c_void_p]),
     "gslm_lm_diag_view": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.POINTER(GslmGaussians), ctypes.c_void_p,
                                          ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64,
                                          ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
@@ -543,8 +551,8 @@ def view_ptr(views, c0=0):
 
 
 def extend_opts(opts, cls, flag):
-    """The options `opts` as the base of an extended struct `cls` (GslmMatvecOptsLean, GslmMatvecOptsExposure) with
-    `flag` set in base.flags -- the library reads the extension behind the base when it sees the flag.  The caller
+    """The options `opts` as the base of an extended struct `cls` (GslmMatvecOptsLean, GslmMatvecOptsExposure,
+    GslmMatvecOptsDamp) with `flag` set in base.flags -- the library reads the extension behind the base when it sees the flag.  The caller
     fills the extension."""
     ext = cls()
     ctypes.memmove(ctypes.addressof(ext.base), ctypes.addressof(opts), ctypes.sizeof(opts))

@@ -33,6 +33,7 @@ MV_TAIL_CLEAN = 1  # gslm_matvec_opts.flags: GSLM_MV_TAIL_CLEAN
 MV_SH_REST_PROJECTED = 2  # GSLM_MV_SH_REST_PROJECTED
 MV_LEAN = 4  # GSLM_MV_LEAN
 MV_EXPOSURE = 8  # GSLM_MV_EXPOSURE
+MV_DAMP_VEC = 16  # GSLM_MV_DAMP_VEC
 DIAG_TAIL_CLEAN = 1  # gslm_lm_diag_view flags: GSLM_DIAG_TAIL_CLEAN
 DIAG_ACCUMULATE = 2  # GSLM_DIAG_ACCUMULATE
 DIAG_SH_REST_PROJECTED = 4  # GSLM_DIAG_SH_REST_PROJECTED
@@ -243,7 +244,10 @@ class _ProductOpts:
         e0, e1 = self.layout.offsets["exposure"]
         if exposure_zero or e1 == e0:
             return
-        if damp:
+        dvec = self._damp_vec() if (damp and hasattr(self, "_damp_vec")) else None
+        if dvec is not None:
+            torch.mul(v[e0:e1], dvec[e0:e1], out=y[e0:e1])
+        elif damp:
             torch.mul(v[e0:e1], float(self._damps[6]), out=y[e0:e1])
         else:
             y[e0:e1].zero_()
@@ -289,7 +293,8 @@ class LMProblem(_ProductOpts):
     """The LM normal equations of one camera batch (one LM step's worth of cached geometry)."""
 
     def __init__(self, model, cams, bg, gts=None, alpha_masks=None, mask_xyz=True, damp=None, device="cuda",
-                 ssim=False, lambda_dssim=0.2, sh_projection=False, train_exposure=False):
+                 ssim=False, lambda_dssim=0.2, sh_projection=False, train_exposure=False, damping="fixed",
+                 marquardt_floor=0.0):
         """ssim=False: the residual train_jvp.py uses (disable_ssim=True, [r; r]); ssim=True: the
         [r1; r2] residual with the SSIM term (batch_training_loss.py:18-30, gslm_ssim_*).
 
@@ -304,7 +309,36 @@ class LMProblem(_ProductOpts):
         sh_projection: param-space vectors carry the SH-rest group as 3 coordinates per Gaussian along the
         view's unit basis direction (GSLM_MV_SH_REST_PROJECTED; one view only -- with one view the CG
         iterates of (J^T J + D) x = J^T b never leave that span).  True / False / "auto" (= one camera and
-        SH degree > 0).  `expand` / `project` convert to and from the reference's layout (`full_layout`)."""
+        SH degree > 0).  `expand` / `project` convert to and from the reference's layout (`full_layout`).
+
+        damping: "fixed" (D = the seven absolute constants of `damp`, the reference's GaussianModelDampMatrix) or
+        "marquardt": D = diag(d), d = lambda[group] max(diag(sum_b 2 J_b^T W_b J_b), marquardt_floor), with `damp` the
+        per-group multiplier lambda -- it must be given (the defaults are absolute values and mean something else).
+        d is built lazily, once after each evaluate(): diagonal(damp=False), then gslm_marquardt_scale, IN THE LAYOUT
+        THE SOLVE RUNS IN.  With one view and sh_projection that is the projected layout, whose SH-rest diagonal is
+        the quadratic form of Bh (x) e_c; on the full layout the SH-rest diagonal is Bh_k^2 times that, which is not
+        a scalar on the group, so the projected layout's span argument does not hold for it and the two layouts
+        define two different operators.  Each is a valid Marquardt scaling of its own coordinates.
+        xyz and the exposure tail have no column in J: their d is lambda marquardt_floor, their right-hand side is
+        zero and the iterates stay zero there.  The plain residual on the LM rows only: ValueError with ssim,
+        train_exposure, mask_xyz=False, or the batched problem.  The lean CG loop does not run under it.
+        set_damping_vector / damping_vector: a caller-supplied per-element D >= 0 in place of either."""
+        if damping not in ("fixed", "marquardt"):
+            raise ValueError(f"damping must be 'fixed' or 'marquardt', got {damping!r}")
+        self.damping = damping
+        self.marquardt_floor = float(marquardt_floor)
+        self._dvec = None  # the damping vector in this problem's layout (Marquardt's, or set_damping_vector's)
+        if damping == "marquardt":
+            if damp is None:
+                raise ValueError("damping='marquardt': damp is the per-group multiplier lambda and must be given "
+                                 "(DEFAULT_DAMP holds absolute values)")
+            if ssim or train_exposure or not mask_xyz:  # (BatchedLMProblem refuses it itself)
+                raise ValueError("damping='marquardt' runs the [r; r] residual on the LM rows of LMProblem "
+                                 "(mask_xyz=True, no SSIM, no trained exposure, not the batched problem)")
+            if not (self.marquardt_floor >= 0.0 and math.isfinite(self.marquardt_floor)):
+                raise ValueError(f"marquardt_floor must be finite and >= 0, got {marquardt_floor!r}")
+        elif self.marquardt_floor != 0.0:
+            raise ValueError("marquardt_floor is an option of damping='marquardt'")
         self.model = model
         self.ssim, self.lambda_dssim = bool(ssim), float(lambda_dssim)
         if self.ssim and not mask_xyz:
@@ -364,6 +398,8 @@ class LMProblem(_ProductOpts):
         """Primal forward of every view; residuals, per-pixel weights and the J^T b seeds from one fused
         epilogue per view (gslm_lm_residual); loss = 2 sum ||r||^2 (device double)."""
         live_masks()  # (a bad GSLM_LIVE_MASKS is refused before the geometry's row map reads it)
+        if self.damping == "marquardt":
+            self._dvec = None  # (the diagonal of the new weights: rebuilt on first use)
         g = raw_gaussians(self.model)
         loss = torch.zeros((), dtype=torch.float64, device=self.device)
         if self.train_exposure:
@@ -580,9 +616,12 @@ class LMProblem(_ProductOpts):
             return y
         last = len(self.views) - 1
         e0, e1 = self.layout.offsets["exposure"]
+        dvec = self._damp_vec() if damp else None
+        if dvec is not None and (lean is not None or self.ssim or self.train_exposure):
+            raise ValueError("a damping vector runs the plain product (no lean loop, SSIM or trained exposure)")
         for b, vr in enumerate(self.views):
             opts = self._opts(vr, STAGE_ALL | (STAGE_OVERWRITE if b == 0 else 0), cg_ctl)
-            opts.damp7 = self._damps if (damp and b == 0) else None
+            opts.damp7 = self._damps if (damp and b == 0 and dvec is None) else None
             if pre is not None and b == 0:
                 ss = self._pre_opts(opts, v, pre)  # noqa: F841  (kept alive for the call)
             fuse = dot_out is not None and b == last
@@ -595,6 +634,10 @@ class LMProblem(_ProductOpts):
                 if lean is not None:
                     raise ValueError("the lean CG loop was written for a zero exposure tail")
                 opts = self._exposure_opts(opts, b, vr, v, y, e0, damp)
+            if dvec is not None and b == 0:  # D v with d per element, on the first view as damp7 is
+                opts = _lib.extend_opts(opts, _lib.GslmMatvecOptsDamp, MV_DAMP_VEC)
+                ds = self.layout.grads_struct(dvec)  # (kept alive for the call)
+                opts.damp_vec = ctypes.addressof(ds)
             self._view_product(vr, g, vs, self.weights[b].data_ptr(), ys, opts, "gslm_matvec_view_ex", lean=lean)
             vr.tail_clean = True
         if self.train_exposure:
@@ -709,7 +752,50 @@ class LMProblem(_ProductOpts):
         return y
 
     def damp_add(self, v, y):
+        dvec = self._damp_vec()
+        if dvec is not None:
+            y.addcmul_(dvec, v)
+            return
         check(lib.gslm_damp_add(v.numel(), v.data_ptr(), self._bounds, self._damps, 7, y.data_ptr(), self.stream))
+
+    # -------------------------------------------------------------- the damping vector (damping="marquardt")
+    def _damp_vec(self):
+        """The damping vector of this problem's products, or None (D is the seven constants): Marquardt's, built on
+        first use after an evaluate(), or the one set_damping_vector holds."""
+        if self._dvec is None and self.damping == "marquardt":
+            self._dvec = self._marquardt_scale(self.diagonal(damp=False))
+        return self._dvec
+
+    def _marquardt_scale(self, diag, out=None):
+        """lambda[group] max(diag, floor) (gslm_marquardt_scale); in place without `out`."""
+        out = diag if out is None else out
+        check(lib.gslm_marquardt_scale(diag.numel(), diag.data_ptr(), self._bounds, self._damps, 7,
+                                       self.marquardt_floor, out.data_ptr(), self.stream), "gslm_marquardt_scale")
+        return out
+
+    def damping_vector(self):
+        """The per-element damping d of the products (this problem's layout), or None under the seven constants.
+        Under damping="marquardt" it needs a current evaluate() and is the vector the next solve uses."""
+        return self._damp_vec()
+
+    def set_damping_vector(self, d):
+        """D = diag(d) for a caller-supplied d >= 0 in this problem's layout (a per-parameter trust region) in place
+        of the seven constants or of Marquardt's vector; None returns to them.  The products, damp_add, the exposure
+        tail, diagonal(damp=True) and the active list use it; the lean CG loop does not run.  Held until replaced --
+        under damping="marquardt" until the next evaluate().  The plain residual on the LM rows of LMProblem only."""
+        if d is None:
+            self._dvec = None
+            return
+        if self.ssim or self.train_exposure or not self.mask_xyz or self.layout.rest_views or self._active is not None:
+            raise ValueError("set_damping_vector: the [r; r] residual on the LM rows of LMProblem (mask_xyz=True, no "
+                             "SSIM, no trained exposure, not the batched problem or an active view)")
+        if (not torch.is_tensor(d) or d.dtype != torch.float32 or d.shape != (self.layout.numel,) or
+                not d.is_contiguous() or d.device != torch.zeros(0, device=self.device).device):
+            raise ValueError(f"set_damping_vector: a contiguous float32 vector of {self.layout.numel} elements on "
+                             f"{self.device}")
+        if bool((d < 0).any()):
+            raise ValueError("set_damping_vector: D must be >= 0")
+        self._dvec = d
 
     # -------------------------------------------------------------- residual-space J and J^T (cgls_residual)
     def residual_masks(self):
@@ -787,6 +873,9 @@ class LMProblem(_ProductOpts):
         act.layout = ParamLayout(na, lay.K, lay.n_exposure, rest_projected=lay.rest_projected,
                                  rest_views=lay.rest_views)
         act._bounds, act._damps = act.layout.group_damp_arrays(self.damp)
+        dvec = self._damp_vec()
+        if dvec is not None:
+            act._dvec = act.pack(dvec)  # (once per solve: the listed rows of d)
         return act
 
     def _pack_args(self):
@@ -845,7 +934,8 @@ class LMProblem(_ProductOpts):
         it, else the reference's): gslm_lm_diag_view per view, the first overwriting and the others accumulating, D
         added once; the exposure tail is D alone.  Needs a current evaluate() (the weights); reuses each view's LM row
         map when it has one and builds it otherwise (the products after it then reuse it).  The plain residual on the
-        LM rows only: ValueError with mask_xyz=False, ssim, train_exposure, or the batched problem's coordinates."""
+        LM rows only: ValueError with mask_xyz=False, ssim, train_exposure, or the batched problem's coordinates.
+        With a damping vector (damping="marquardt", set_damping_vector) damp=True adds d: diag + d."""
         if (not self.mask_xyz or self.ssim or self.train_exposure or self.layout.rest_views or
                 self._active is not None):
             raise ValueError("diagonal: the [r; r] residual on the LM rows (mask_xyz=True, no SSIM, no trained "
@@ -853,6 +943,12 @@ class LMProblem(_ProductOpts):
         if any(w is None for w in self.weights):
             raise RuntimeError("diagonal: no current evaluate() (the per-pixel weights)")
         out = torch.empty(self.layout.numel, dtype=torch.float32, device=self.device) if out is None else out
+        if damp and (self._dvec is not None or self.damping == "marquardt"):
+            # D = diag(d): the diagonal of the matrix the products apply is diag + d
+            self.diagonal(out, damp=False)
+            if self._dvec is None:
+                self._dvec = self._marquardt_scale(out, torch.empty_like(out))
+            return out.add_(self._dvec)
         g = raw_gaussians(self.model)
         ys = self.layout.grads_struct(out)
         for b, vr in enumerate(self.views):
@@ -890,7 +986,10 @@ class BatchedLMProblem(LMProblem, _StageTimes):
     STAGES = ("tangent_views", "tile_passes", "gather_views")  # (_StageTimes.stage_times)
 
     def __init__(self, model, cams, bg, gts=None, alpha_masks=None, mask_xyz=True, damp=None, device="cuda",
-                 ssim=False, lambda_dssim=0.2, sh_projection=False, union_active=False):
+                 ssim=False, lambda_dssim=0.2, sh_projection=False, union_active=False, damping="fixed",
+                 marquardt_floor=0.0):
+        if damping != "fixed" or marquardt_floor != 0.0:
+            raise ValueError("BatchedLMProblem runs the fixed damping (damping='marquardt' is LMProblem's)")
         if not mask_xyz:
             raise ValueError("BatchedLMProblem runs on the LM rows (mask_xyz=True, train_jvp.py:221-227)")
         if ssim:
@@ -1153,6 +1252,8 @@ def _lean_applies(act, check_every, max_iter):
         return False  # (the lean loop is the single view's: act.views[0], its parameter block)
     if getattr(act, "train_exposure", False):
         return False  # (the lean kernels were written for a zero exposure tail)
+    if getattr(act, "_dvec", None) is not None or getattr(act, "damping", "fixed") != "fixed":
+        return False  # (a damping vector: the lean gather reads the seven constants)
     return (not check_every and max_iter >= 1 and not act.ssim and getattr(act, "allreduce_scalars", None) is None
             and os.environ.get("GSLM_CG_LEAN", "1") != "0")
 
@@ -1516,6 +1617,8 @@ def cgls_residual(prob, max_iter=10, restart_iter=10, tol=1e-10, atol=0.0, verbo
     rounding path.  b = -[r; r] (train_jvp.py:243), x0 = 0.  Returns (x, info)."""
     if getattr(prob, "ssim", False):
         raise ValueError("cgls_residual: the disable_ssim residual only")
+    if getattr(prob, "damping", "fixed") != "fixed" or getattr(prob, "_dvec", None) is not None:
+        raise ValueError("cgls_residual: the seven damping constants only (no damping vector)")
     if getattr(prob, "train_exposure", False):
         raise ValueError("cgls_residual: the residual-space recursion does not carry trained exposure")
     dev = prob.device
@@ -2089,7 +2192,8 @@ def clear_val_cache():
 def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, mask_xyz=True, check_every=True,
             verbose=False, device="cuda", sh_projection="auto", recursion="fused", exchange="auto", group=None,
             val_batch=8, timing=False, backend=None, line_search="union", val_at_start=False, cache_val=True,
-            multiview="loop", union_active=False, train_exposure=False, val_exposure="forward", precond=None):
+            multiview="loop", union_active=False, train_exposure=False, val_exposure="forward", precond=None,
+            damping="fixed", marquardt_floor=0.0):
     """One LM step of train_jvp.py:237-289: loss, CGLS on the normal equations, backtracking line search.
 
     Single process: LMProblem over `cams` (with one training view the SH-rest group of the CG vectors is carried
@@ -2130,6 +2234,11 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     diag(J^T J + D), LMProblem.diagonal; the result and its cg info report precond="jacobi").  Any other string raises
     ValueError, and so does "jacobi" with recursion="cgls", train_exposure=True, multiview="batched", a sharded run,
     mask_xyz=False or a backend (the SSIM residual, which lm_step does not run, is refused by cgls_jacobi itself).
+    damping: "fixed" (today's step, launch for launch) or "marquardt" (LMProblem(damping="marquardt"): D = lambda
+    max(diag(J^T W J), marquardt_floor) in the layout the solve runs in, `damp` the per-group lambda, which must be
+    given).  The single-process step with multiview="loop", recursion="fused", mask_xyz=True, no trained exposure and
+    no backend, with either precond -- anything else, another string, or a marquardt_floor without it raises
+    ValueError.  The result reports `damping`.
     backend: (problem_cls, evaluator_cls, solver) replacing (LMProblem, LossEvaluator, cgls_fused) -- the CPU
     multi-process tests run this same driver, sharding and reductions on the oracle restatement."""
     import time
@@ -2162,7 +2271,19 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
             raise ValueError("precond='jacobi' is the single-process step with multiview='loop', recursion='fused', "
                              "mask_xyz=True and no trained exposure")
         solver = cgls_jacobi
+    if damping not in ("fixed", "marquardt"):
+        raise ValueError(f"damping must be 'fixed' or 'marquardt', got {damping!r}")
+    if damping == "marquardt":
+        if (sharded or backend is not None or recursion != "fused" or not mask_xyz or train_exposure or
+                multiview != "loop"):
+            raise ValueError("damping='marquardt' is the single-process step with multiview='loop', recursion='fused', "
+                             "mask_xyz=True, no trained exposure and no backend")
+        if damp is None:
+            raise ValueError("damping='marquardt': damp is the per-group multiplier lambda and must be given")
+    elif marquardt_floor != 0.0:
+        raise ValueError("marquardt_floor is an option of damping='marquardt'")
     exp_kw = {"train_exposure": True} if train_exposure else {}
+    damp_kw = {"damping": "marquardt", "marquardt_floor": marquardt_floor} if damping == "marquardt" else {}
     fused_exposure = val_exposure == "fused"
     t = {}
     clock = [time.perf_counter()]
@@ -2184,7 +2305,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     else:
         kw = {"union_active": True} if (union_active and problem_cls is BatchedLMProblem) else {}
         prob = problem_cls(model, cams, bg, mask_xyz=mask_xyz, damp=damp, device=device, sh_projection=sh_projection,
-                           **kw, **exp_kw)
+                           **kw, **exp_kw, **damp_kw)
     start_loss = prob.evaluate()
     if recursion == "cgls":
         lap("evaluate_rhs_ms")
@@ -2272,6 +2393,8 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
                val_views=len(val_cams), ranks=n if sharded else 1, line_search="union" if union else "exact")
     if precond is not None:
         out["precond"] = precond
+    if damping != "fixed":
+        out["damping"] = damping
     if val_at_start:
         out["val_start_loss"] = val_start
     if union and getattr(val, "union_counts", None):

@@ -693,6 +693,32 @@ int gslm_dot_finalize(const void* partials, int32_t np, double* out_dev, void* s
 int gslm_damp_add(int64_t n, const float* x, const int64_t* group_bounds, const double* group_damp,
                   int32_t ngroups, float* y, void* stream);
 
+/* ---- Marquardt-scaled damping D = lambda diag(J^T W J) (additive entry points, still ABI 9) ----
+ * gslm_marquardt_scale: d[i] = (float)lambda[group(i)] * max(diag[i], floor) on a flat vector of n floats -- the
+ * damping vector of a diagonal (gslm_lm_diag_view without damp7).  Groups as gslm_dot / gslm_damp_add: bounds[0 ..
+ * ngroups], ngroups <= 8, host arrays (an element outside every group gets 0; ngroups = 0: lambda = 1); groups of
+ * zero width and n = 0 are legal.  The max is the select diag < floor ? floor : diag, so a NaN diagonal gives a NaN
+ * d (which the solve's non-finite checks then meet).  d may be diag.  GSLM_ERR_INVALID, nothing launched: n < 0,
+ * a floor that is negative, NaN or beyond float, more than 8 groups, a NULL group array with ngroups > 0, or a NULL
+ * vector with n > 0. */
+int gslm_marquardt_scale(int64_t n, const float* diag, const int64_t* group_bounds, const double* group_lambda,
+                         int32_t ngroups, double floor, float* d, void* stream);
+/* GSLM_MV_DAMP_VEC in opts->flags: opts points to the base member of a gslm_matvec_opts_damp, and GATHER forms
+ *   y = [y_old +] J^T(...) + d (.) v
+ * with d read per element from damp_vec: a flat param-space vector with the groups and strides of v and y (the
+ * projected SH-rest group included; on an active list, the listed rows).  Per element the arithmetic is damp7's --
+ * val + d v, a multiply and an add -- so a d that is constant per group gives damp7's y and dot_vy bitwise; dot_vy
+ * includes the term.  The xyz group (mask_xyz) is written d (.) v, as damp7's.  Accepted by gslm_matvec_view_ex and
+ * gslm_matvec_view_active; gslm_gather_views, gslm_gather_views_active and gslm_gather_screen refuse the flag.
+ * GSLM_ERR_INVALID before anything is launched (outputs untouched): with a non-NULL damp7; a NULL damp_vec or a
+ * NULL group of it (sh_rest excepted when max_coeffs = 1) or SH strides other than y's; pixel_seed, jv_out,
+ * GSLM_STAGE_SCREEN, trec_in or rest_basis; GSLM_MV_LEAN or GSLM_MV_EXPOSURE; mask_xyz = 0. */
+#define GSLM_MV_DAMP_VEC 16
+typedef struct gslm_matvec_opts_damp {
+  gslm_matvec_opts base;
+  const gslm_grads* damp_vec;
+} gslm_matvec_opts_damp;
+
 /* ---- diag(J^T W J + D) and Jacobi-preconditioned CG (additive entry points, still ABI 9) ----
  * gslm_lm_diag_view: the diagonal of the matrix gslm_matvec_view_ex applies for one view with mask_xyz (the
  * reference's matvec / matvec_T pair, solver/solver_functions.py:83-132, on the [r; r] residual):
