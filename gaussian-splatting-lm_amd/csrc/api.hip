@@ -147,11 +147,16 @@ static int make_gauss(const gslm_gaussians* in, const ViewK* v, GaussK* g, bool 
   return GSLM_OK;
 }
 
+// the preprocess kernels' outputs inside a geometry workspace; pos: the view's depth positions, or NULL (index space)
+static PreOutBufs pre_out_bufs(const GeomBufs& gb, const uint32_t* pos) {
+  return PreOutBufs{gb.rec, gb.depth_key, gb.tiles, gb.rect, gb.clampw, pos};
+}
+
 // order_mode (gslm_preprocess_ordered): 0 sort, 1 sort and copy the order out to depth_order, 2 take the order from
 // depth_order instead of sorting
 int do_preprocess(const ViewK& v, const GaussK& g, const GeomBufs& gb, int32_t* radii, hipStream_t s,
-                  uint32_t* depth_order = nullptr, int order_mode = 0) {
-  int st = launch_preprocess(v, g, gb, radii, s);
+                  uint32_t* depth_order, int order_mode) {
+  int st = launch_preprocess(v, g, pre_out_bufs(gb, nullptr), radii, s);
   if (st) return st;
   const int64_t P = g.P;
   if (P == 0) {
@@ -238,24 +243,9 @@ size_t gslm_binning_bytes(int64_t N, int32_t H, int32_t W) {
 }
 size_t gslm_scratch_bytes(int64_t P, int64_t N) { return scratch_layout(P, N, nullptr, nullptr); }
 
-int gslm_preprocess(const gslm_view* view, const gslm_gaussians* gi, void* geom, size_t geom_bytes, int32_t* out_radii,
-                    void* stream) {
-  DebugScope dbg_scope(view != nullptr && view->debug != 0, stream);
-  ViewK v;
-  GaussK g;
-  int st = make_view(view, gi ? gi->max_coeffs : 0, &v);
-  if (st) return st;
-  if ((st = make_gauss(gi, &v, &g, false))) return st;
-  if (geom_bytes < gslm_geom_bytes(g.P) || (!geom && g.P)) { set_error("geometry workspace too small"); return GSLM_ERR_CAPACITY; }
-  GeomBufs gb;
-  geom_layout(g.P, geom, &gb);
-  return do_preprocess(v, g, gb, out_radii, (hipStream_t)stream);
-}
-
-int gslm_preprocess_ordered(const gslm_view* view, const gslm_gaussians* gi, void* geom, size_t geom_bytes,
-                            int32_t* out_radii, uint32_t* depth_order, int32_t order_mode, void* stream) {
-  if (order_mode < 0 || order_mode > 2) { set_error("preprocess_ordered: order_mode must be 0, 1 or 2"); return GSLM_ERR_INVALID; }
-  if (order_mode && gi && gi->P > 0 && !depth_order) { set_error("preprocess_ordered: NULL depth_order"); return GSLM_ERR_INVALID; }
+// gslm_preprocess and its ordered form: one body, order_mode 0 for the plain one
+static int preprocess(const gslm_view* view, const gslm_gaussians* gi, void* geom, size_t geom_bytes, int32_t* out_radii,
+                      uint32_t* depth_order, int32_t order_mode, void* stream) {
   ViewK v;
   GaussK g;
   int st = make_view(view, gi ? gi->max_coeffs : 0, &v);
@@ -267,6 +257,19 @@ int gslm_preprocess_ordered(const gslm_view* view, const gslm_gaussians* gi, voi
   return do_preprocess(v, g, gb, out_radii, (hipStream_t)stream, depth_order, order_mode);
 }
 
+int gslm_preprocess(const gslm_view* view, const gslm_gaussians* gi, void* geom, size_t geom_bytes, int32_t* out_radii,
+                    void* stream) {
+  DebugScope dbg_scope(view != nullptr && view->debug != 0, stream);
+  return preprocess(view, gi, geom, geom_bytes, out_radii, nullptr, 0, stream);
+}
+
+int gslm_preprocess_ordered(const gslm_view* view, const gslm_gaussians* gi, void* geom, size_t geom_bytes,
+                            int32_t* out_radii, uint32_t* depth_order, int32_t order_mode, void* stream) {
+  if (order_mode < 0 || order_mode > 2) { set_error("preprocess_ordered: order_mode must be 0, 1 or 2"); return GSLM_ERR_INVALID; }
+  if (order_mode && gi && gi->P > 0 && !depth_order) { set_error("preprocess_ordered: NULL depth_order"); return GSLM_ERR_INVALID; }
+  return preprocess(view, gi, geom, geom_bytes, out_radii, depth_order, order_mode, stream);
+}
+
 int gslm_preprocess_views(const gslm_view* views, int32_t nviews, const gslm_gaussians* gi, void* const* geoms,
                           size_t geom_bytes, const uint32_t* const* depth_pos, void* stream) {
   if (!views || !gi || !geoms || nviews < 1 || nviews > MAX_PRE_VIEWS) {
@@ -274,7 +277,6 @@ int gslm_preprocess_views(const gslm_view* views, int32_t nviews, const gslm_gau
     return GSLM_ERR_INVALID;
   }
   PreViewsK pv;
-  GeomBufs gbs[MAX_PRE_VIEWS];
   GaussK g;
   int st;
   for (int b = 0; b < nviews; ++b) {
@@ -282,13 +284,14 @@ int gslm_preprocess_views(const gslm_view* views, int32_t nviews, const gslm_gau
     if ((st = make_gauss(gi, &pv.v[b], &g, false))) return st;  // each view's SH degree against the stored coefficients
     const size_t need = depth_pos ? depth_records_bytes(g.P) : gslm_geom_bytes(g.P);
     if (geom_bytes < need || (!geoms[b] && g.P)) { set_error("geometry workspace too small"); return GSLM_ERR_CAPACITY; }
-    geom_layout(g.P, geoms[b], &gbs[b]);  // depth space writes the records (offset 0) only
+    GeomBufs gb;
+    geom_layout(g.P, geoms[b], &gb);  // depth space writes the records (offset 0) only
     const uint32_t* pos = depth_pos ? depth_pos[b] : nullptr;
     if (depth_pos && !pos && g.P) { set_error("preprocess_views: NULL depth positions"); return GSLM_ERR_INVALID; }
-    pv.out[b] = PreOutBufs{gbs[b].rec, gbs[b].depth_key, gbs[b].tiles, gbs[b].rect, gbs[b].clampw, pos};
+    pv.out[b] = pre_out_bufs(gb, pos);
   }
   pv.n = nviews;
-  return launch_preprocess_views(pv, g, gbs, (hipStream_t)stream);
+  return launch_preprocess_views(pv, g, (hipStream_t)stream);
 }
 
 int gslm_depth_positions(const uint32_t* depth_order, int64_t P, uint32_t* depth_pos, void* stream) {

@@ -1,13 +1,24 @@
 // forward.hip -- rasterizer forward for gfx950.
 //
-//   k_preprocess   one thread per Gaussian: cull, project, cov3D, EWA cov2D, conic, radius,
-//                  rect, SH->RGB; writes a 48-B render record (64-B stride) + depth key + tile count.
+//   k_preprocess, k_preprocess_dma, k_preprocess_views
+//                  one thread per Gaussian: cull, project, cov3D, EWA cov2D, conic, radius, rect, SH->RGB; writes a
+//                  48-B render record (64-B stride, the rect again in its fourth slot) + depth key + tile count + rect
+//                  + clamp word.  Three kernels (SH rows read from global memory / staged by LDS-DMA / several views
+//                  per pass) written from the shared parts above them: write_record, write_index_outputs,
+//                  pin_pre_in, stage_sh_dma_begin / stage_sh_dma_finish.
 //   (depth sort of P keys + scan of tile counts in depth order: sort.hip)
 //   k_duplicate    emits (tile id, Gaussian id) pairs in depth order: the later *stable* sort on
 //                  the tile id alone then yields upstream's (tile, depth, index) order with
 //                  2 radix passes over N_dup instead of 6 (SURVEY §7 "Sort"); the sorted values
 //                  ARE the point list.
 //   k_ranges       per-tile [start, end) from key changes (identifyTileRanges).
+//   k_tile_order, k_tile_order_xcd   the tile passes' launch order (longest list first; XCD-banded for the LM product).
+//   k_point_ids    the Gaussian ids of a point list (its quadrant masks stripped).
+//   k_tile_neff, k_tile_cost, k_quad_live, k_row_flags, k_row_final   the LM row map and the LM product's tile cost.
+//   k_active_flags, k_active_scatter, k_union_flags, k_union_scatter   the active Gaussians of one view / of a batch.
+//   k_depth_positions, k_union_rect, k_duplicate_union   the line search's union binning in depth space.
+//   launchers: launch_preprocess(_views), launch_binning, launch_ranges, launch_tile_order, launch_lm_rowmap,
+//   launch_active_list / _union, launch_depth_positions, launch_union_rect / _binning, launch_point_ids.
 //   (k_render_fwd, the per-tile blend: render_fwd.hip)
 #include "gslm_internal.hpp"
 #include "gslm_kernels.hpp"
@@ -15,180 +26,174 @@
 
 namespace gslm {
 
-// STAGE: the block's SH-rest rows (3(M-1) floats per Gaussian, contiguous: the GaussianModel leaf) are
-// staged through LDS with coalesced float4 loads first -- per-thread reads at a 180-B stride made every
-// load instruction touch 64 cache lines (k_preprocess ran at ~2.2 TB/s).
-template <bool RAW, bool STAGE>
-__global__ __launch_bounds__(256) void k_preprocess(ViewK v, GaussK g, float4* __restrict__ rec,
-                                                     uint32_t* __restrict__ depth_key,
-                                                     uint32_t* __restrict__ tiles, uint2* __restrict__ rect,
-                                                     uint32_t* __restrict__ clampw, int* __restrict__ radii_out,
-                                                     int lead) {
-  extern __shared__ __attribute__((aligned(16))) float s_sh[];  // STAGE: [256 * rest_stride]
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (STAGE) {
-    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x;
-    const int64_t nv = min((int64_t)blockDim.x, g.P - i0);
-    const int64_t total = nv * g.rest_stride;  // floats; i0 * rest_stride * 4 B is 16-B aligned (i0 % 256 == 0)
-    const float* rows = g.rest - lead + i0 * g.rest_stride;  // stage_lead
-    const float4* src4 = reinterpret_cast<const float4*>(rows);
-    float4* dst4 = reinterpret_cast<float4*>(s_sh);
-    for (int64_t e = threadIdx.x; e < total / 4; e += blockDim.x) dst4[e] = src4[e];
-    for (int64_t e = (total / 4) * 4 + threadIdx.x; e < total; e += blockDim.x) s_sh[e] = rows[e];
-    __syncthreads();
-    g.rest = s_sh + lead;
-    g.rest_base = i0;
-  }
-  if (i >= g.P) return;
-  tiles[i] = 0u;
-  depth_key[i] = 0xFFFFFFFFu;
-  if (radii_out) radii_out[i] = 0;
-  PreOut o;
-  o.depth = 0.f;
-  const bool vis = preprocess_one<RAW>(v, g, i, o);
-  // Every Gaussian in front of the near plane gets its depth key, culled by its footprint or not: the depth order
-  // then depends on means3D and the view alone, so one view's order is reusable while xyz is unchanged (the LM
-  // step freezes xyz, train_jvp.py:221-227: gslm_preprocess_ordered).  The point list is the same either way
-  // (Gaussians culled later emit no tile).
-  if (o.depth > 0.2f) depth_key[i] = __float_as_uint(o.depth);
-  if (!vis) return;
+// ------------------------------------------------------------------ the preprocess kernels' shared parts
+// The arithmetic is gslm_kernels.hpp's (load_pre_in, preprocess_core, preprocess_color); the parts below are what the
+// three kernels do around it.  Each is block-uniform only where it says so.
 
-  const float4 r0 = make_float4(o.x, o.y, o.conic[0], o.conic[1]);
-  const float4 r1 = make_float4(o.conic[2], o.opac, o.rgb[0], o.rgb[1]);
-  const float4 r2 = make_float4(o.rgb[2], 1.0f / o.depth, __uint_as_float(o.clamped), o.tq);
-  rec[RECS * i + 0] = r0;
-  rec[RECS * i + 1] = r1;
-  rec[RECS * i + 2] = r2;
-  tiles[i] = (uint32_t)((o.rmax_x - o.rmin_x) * (o.rmax_y - o.rmin_y));
-  const uint2 rc = make_uint2((uint32_t)o.rmin_x | ((uint32_t)o.rmin_y << 16), (uint32_t)o.rmax_x | ((uint32_t)o.rmax_y << 16));
-  rect[i] = rc;
-  // the rect again in the record's padding slot: k_duplicate's random per-Gaussian read is then one 64-B record
-  // (one cache line) instead of the record and a rect line
-  rec[RECS * i + 3] = make_float4(__uint_as_float(rc.x), __uint_as_float(rc.y), 0.f, 0.f);
-  clampw[i] = o.clamped;  // read only where tiles[i] != 0
+// The rect as k_duplicate and row_slot read it: min | max, x in the low and y in the high 16 bits.
+__device__ __forceinline__ uint2 pack_rect(const PreOut& o) {
+  return make_uint2((uint32_t)o.rmin_x | ((uint32_t)o.rmin_y << 16), (uint32_t)o.rmax_x | ((uint32_t)o.rmax_y << 16));
+}
+
+// The 64-B render record of one visible Gaussian at `rec` (index space: rec + RECS * i; depth space: rec + RECS *
+// pos[i]): three float4 of (x, y, conic | opacity, rgb | 1/depth, clamp word, tq) and the rect again in the fourth slot
+// -- k_duplicate's random per-Gaussian read is then one 64-B record (one cache line) instead of the record and a rect
+// line.  The only place that knows the record's layout on the writing side.
+__device__ __forceinline__ void write_record(float4* __restrict__ rec, const PreOut& o) {
+  const uint2 rc = pack_rect(o);
+  rec[0] = make_float4(o.x, o.y, o.conic[0], o.conic[1]);
+  rec[1] = make_float4(o.conic[2], o.opac, o.rgb[0], o.rgb[1]);
+  rec[2] = make_float4(o.rgb[2], 1.0f / o.depth, __uint_as_float(o.clamped), o.tq);
+  rec[3] = make_float4(__uint_as_float(rc.x), __uint_as_float(rc.y), 0.f, 0.f);
+}
+// A culled Gaussian's record in depth space: the zero rect slot alone (an empty rect; the union binning reads no other
+// slot of it).  Index space writes nothing for a culled Gaussian: its tile count is 0 and nothing reads its record.
+__device__ __forceinline__ void write_culled_record(float4* __restrict__ rec) {
+  rec[3] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
+
+// Every index-space output of Gaussian i, once: tile count, depth key, radius (where asked for) and, when visible, the
+// record, the rect and the clamp word (both read only where tiles[i] != 0).  o.depth must be set whether visible or not
+// (preprocess_core sets it before any cull), o's other fields only when visible.
+// The depth key: the depth's bits for every Gaussian in front of the near plane, culled by its footprint or not, and
+// 0xFFFFFFFF otherwise.  The depth order then depends on means3D and the view alone, so one view's order is reusable
+// while xyz is unchanged (the LM step freezes xyz: gslm_preprocess_ordered).  The point list is the same either way
+// (Gaussians culled later emit no tile).
+__device__ __forceinline__ void write_index_outputs(const PreOutBufs& ob, int* __restrict__ radii_out, int64_t i,
+                                                    bool vis, const PreOut& o) {
+  ob.depth_key[i] = o.depth > 0.2f ? __float_as_uint(o.depth) : 0xFFFFFFFFu;
+  if (!vis) {
+    ob.tiles[i] = 0u;
+    if (radii_out) radii_out[i] = 0;
+    return;
+  }
+  write_record(ob.rec + RECS * i, o);
+  ob.tiles[i] = (uint32_t)((o.rmax_x - o.rmin_x) * (o.rmax_y - o.rmin_y));
+  ob.rect[i] = pack_rect(o);
+  ob.clampw[i] = o.clamped;
   if (radii_out) radii_out[i] = o.radius;
 }
 
-// k_preprocess with the block's SH-rest rows staged by LDS-DMA (global_load_lds_dwordx4: 1 KiB per wave-instruction,
-// no VGPR round trip) and the staging overlapped with the geometry: every thread loads its Gaussian's geometry
-// inputs first (and waits for them), the waves then issue the block's DMA chunks, run the geometry arithmetic
-// (cull, EWA, conic, radius, rect) while the rows land, and meet at one barrier before the colour.  The register
-// path (k_preprocess<_, true>) keeps one 16-B load per thread in flight per round trip of its staging loop.
-// Same arithmetic in the same order: bitwise the same records.
+// Keeps the loads of `in` (and the wait for them) ahead of whatever follows: hipcc waits vmcnt(0) at the first use of
+// an ordinary load issued while an LDS-DMA is outstanding, so inputs still in flight behind the DMA would make the
+// geometry wait for the rows.  Emits no instruction.
+__device__ __forceinline__ void pin_pre_in(const PreIn& in) {
+  asm volatile("" : : "v"(in.x), "v"(in.y), "v"(in.z), "v"(in.c[0]), "v"(in.c[1]), "v"(in.c[2]), "v"(in.c[3]),
+               "v"(in.c[4]), "v"(in.c[5]), "v"(in.qw), "v"(in.op));
+}
+
 __device__ __forceinline__ void glds16(const float4* src, float4* lds_dst) {
   __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
                                    (__attribute__((address_space(3))) void*)lds_dst, 16, 0, 0);
 }
 
-template <bool RAW>
-__global__ __launch_bounds__(256) void k_preprocess_dma(ViewK v, GaussK g, float4* __restrict__ rec,
-                                                         uint32_t* __restrict__ depth_key,
-                                                         uint32_t* __restrict__ tiles, uint2* __restrict__ rect,
-                                                         uint32_t* __restrict__ clampw, int* __restrict__ radii_out,
-                                                         int lead) {
-  extern __shared__ __attribute__((aligned(16))) float s_sh[];  // [256 * rest_stride]
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+// The block's SH-rest rows staged in LDS by LDS-DMA (global_load_lds_dwordx4: 1 KiB per wave-instruction, no VGPR
+// round trip), in two halves with the geometry between them.  The order is the contract:
+//   1. every thread has loaded and pinned its Gaussian's inputs (load_pre_in, pin_pre_in);
+//   2. stage_sh_dma_begin issues the DMA;
+//   3. the geometry (preprocess_core, no colour) runs while the rows land;
+//   4. stage_sh_dma_finish: the barrier, the tail, g.rest pointed at the copy;
+//   5. the colour (preprocess_color) reads the rows from LDS.
+// Both are block-uniform: every thread of a 256-thread block calls them, live or not, before any early return.
+// The span: [nv][g.rest_stride] floats from `lead` floats before the block's first rest row (stage_lead: 16-B
+// aligned there, and i0 * rest_stride * 4 B is a multiple of 16 as i0 % 256 == 0), copied to s_rows[0 ..) --
+// 256 * rest_stride floats of dynamic LDS.
+struct ShSpan {
+  const float* rows;  // the span in global memory
+  int64_t total, n4;  // its floats, its whole float4s
+};
+
+// Issues the span's whole float4s: 64-float4 chunks, chunk c by wave c % 4.  A lane past the last float4 re-reads the
+// last one: the clamp to n4 - 1 keeps every source address inside the span.  (Its LDS slot lies behind the span's
+// whole float4s and inside the 256 rows, as ceil(n4 / 64) <= rest_stride; finish's tail overwrites the floats of it
+// that are read.)  n4 == 0 (a last block of one short row) issues nothing: the loop is left before the clamp could
+// form index -1.
+__device__ __forceinline__ ShSpan stage_sh_dma_begin(const GaussK& g, int lead, float* s_rows) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t i0 = (int64_t)blockIdx.x * blockDim.x;
-  const int64_t i = i0 + tid;
-  const bool live = i < g.P;
-  // 1. this Gaussian's geometry inputs, waited for before any DMA is in flight (hipcc waits vmcnt(0) at the first
-  //    use of an ordinary load issued while an LDS-DMA is outstanding)
-  PreIn in{};
-  if (live) load_pre_in<RAW>(g, i, in);
-  asm volatile("" : : "v"(in.x), "v"(in.y), "v"(in.z), "v"(in.c[0]), "v"(in.c[1]), "v"(in.c[2]), "v"(in.c[3]),
-               "v"(in.c[4]), "v"(in.c[5]), "v"(in.qw), "v"(in.op));
-  // 2. the block's SH-rest rows, [nv][rest_stride] floats, contiguous in the leaf: 64-float4 chunks per wave
   const int64_t nv = min((int64_t)blockDim.x, g.P - i0);
-  const int64_t total = nv * g.rest_stride;  // i0 * rest_stride * 4 B is 16-B aligned (i0 % 256 == 0)
-  const int64_t n4 = total / 4;
-  const float* rows = g.rest - lead + i0 * g.rest_stride;  // stage_lead
-  const float4* src4 = reinterpret_cast<const float4*>(rows);
-  float4* dst4 = reinterpret_cast<float4*>(s_sh);
-  for (int64_t c = w; c * 64 < n4; c += 4) {
-    const int64_t e = min(c * 64 + lane, n4 - 1);  // past the rows: re-read the last float4 (its slot is unused)
+  ShSpan sp;
+  sp.total = nv * g.rest_stride;
+  sp.n4 = sp.total / 4;
+  sp.rows = g.rest - lead + i0 * g.rest_stride;
+  const float4* src4 = reinterpret_cast<const float4*>(sp.rows);
+  float4* dst4 = reinterpret_cast<float4*>(s_rows);
+  for (int64_t c = w; c * 64 < sp.n4; c += 4) {
+    const int64_t e = min(c * 64 + lane, sp.n4 - 1);
     glds16(src4 + e, dst4 + c * 64);
   }
-  // 3. the geometry while the rows land
-  PreOut o;
-  o.depth = 0.f;
-  const bool vis = live && preprocess_core<RAW, false>(v, g, i, in, o);
-  // 4. the DMA landed (the barrier's vmcnt(0)); a row tail that is not a whole float4 (last block only) by plain loads
+  return sp;
+}
+
+// The DMA has landed after the barrier (its vmcnt(0)); a span that is not a whole number of float4 (the last block
+// only) gets its last 1-3 floats by plain loads and a second barrier.  Then g reads the block's rows from LDS.
+__device__ __forceinline__ void stage_sh_dma_finish(GaussK& g, int lead, float* s_rows, const ShSpan& sp) {
   __syncthreads();
-  if (n4 * 4 < total) {
-    for (int64_t e = n4 * 4 + tid; e < total; e += blockDim.x) s_sh[e] = rows[e];
+  if (sp.n4 * 4 < sp.total) {
+    for (int64_t e = sp.n4 * 4 + threadIdx.x; e < sp.total; e += blockDim.x) s_rows[e] = sp.rows[e];
     __syncthreads();
   }
+  g.rest = s_rows + lead;
+  g.rest_base = (int64_t)blockIdx.x * blockDim.x;
+}
+
+// ------------------------------------------------------------------ the preprocess kernels
+// The SH rows read from global memory: the kernel of the layouts stage_lead refuses (colours given, degree 0, an
+// unaligned or padded rest).
+template <bool RAW>
+__global__ __launch_bounds__(256) void k_preprocess(ViewK v, GaussK g, PreOutBufs ob, int* __restrict__ radii_out) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= g.P) return;
+  PreOut o;
+  const bool vis = preprocess_one<RAW>(v, g, i, o);
+  write_index_outputs(ob, radii_out, i, vis, o);
+}
+
+// k_preprocess with the block's SH-rest rows staged by LDS-DMA and the staging overlapped with the geometry
+// (stage_sh_dma_begin's contract).  Per-thread reads of the rows at a 180-B stride made every load instruction touch
+// 64 cache lines (the unstaged kernel ran at ~2.2 TB/s on the contiguous leaf).  Same arithmetic in the same order:
+// bitwise the same records.
+template <bool RAW>
+__global__ __launch_bounds__(256) void k_preprocess_dma(ViewK v, GaussK g, PreOutBufs ob, int* __restrict__ radii_out,
+                                                         int lead) {
+  extern __shared__ __attribute__((aligned(16))) float s_sh[];  // [256 * rest_stride]
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = i < g.P;
+  PreIn in{};
+  if (live) load_pre_in<RAW>(g, i, in);
+  pin_pre_in(in);
+  const ShSpan sp = stage_sh_dma_begin(g, lead, s_sh);
+  PreOut o;
+  const bool vis = live && preprocess_core<RAW, false>(v, g, i, in, o);
+  stage_sh_dma_finish(g, lead, s_sh, sp);
   if (!live) return;
-  tiles[i] = 0u;
-  depth_key[i] = 0xFFFFFFFFu;
-  if (radii_out) radii_out[i] = 0;
-  if (o.depth > 0.2f) depth_key[i] = __float_as_uint(o.depth);  // as k_preprocess: every Gaussian before the near plane
-  if (!vis) return;
-  g.rest = s_sh + lead;
-  g.rest_base = i0;
-  preprocess_color(v, g, i, in, o);
-  const float4 r0 = make_float4(o.x, o.y, o.conic[0], o.conic[1]);
-  const float4 r1 = make_float4(o.conic[2], o.opac, o.rgb[0], o.rgb[1]);
-  const float4 r2 = make_float4(o.rgb[2], 1.0f / o.depth, __uint_as_float(o.clamped), o.tq);
-  rec[RECS * i + 0] = r0;
-  rec[RECS * i + 1] = r1;
-  rec[RECS * i + 2] = r2;
-  tiles[i] = (uint32_t)((o.rmax_x - o.rmin_x) * (o.rmax_y - o.rmin_y));
-  const uint2 rc = make_uint2((uint32_t)o.rmin_x | ((uint32_t)o.rmin_y << 16), (uint32_t)o.rmax_x | ((uint32_t)o.rmax_y << 16));
-  rect[i] = rc;
-  // the rect again in the record's padding slot: k_duplicate's random per-Gaussian read is then one 64-B record
-  // (one cache line) instead of the record and a rect line
-  rec[RECS * i + 3] = make_float4(__uint_as_float(rc.x), __uint_as_float(rc.y), 0.f, 0.f);
-  clampw[i] = o.clamped;
-  if (radii_out) radii_out[i] = o.radius;
+  if (vis) preprocess_color(v, g, i, in, o);
+  write_index_outputs(ob, radii_out, i, vis, o);
 }
 
 // k_preprocess_dma for up to MAX_PRE_VIEWS views in one pass over the Gaussians (gslm_preprocess_views: the line
 // search's parameter sets over a batch of validation views).  A view's inputs cost 236 B per Gaussian at SH 3 against
 // 84 B of its outputs; the block loads its Gaussians' inputs and stages their SH rows once, then writes every view's
-// records, depth keys, tile counts and rects from them.  Per view the same functions in the same order as
-// k_preprocess_dma: bitwise the same geometry.
-// STAGE: the block's SH-rest rows are staged in LDS by LDS-DMA (views_pass_ok); otherwise (SH degree 0, colours or
-// cov3D given, an odd layout) every view reads its inputs from global memory -- the same outputs, depth space included.
+// outputs from them.  Per view the same functions in the same order as k_preprocess_dma: bitwise the same geometry.
+// STAGE: the rows are staged (views_pass_ok: lead 0); otherwise (SH degree 0, colours or cov3D given, an odd layout)
+// every view reads its inputs from global memory -- the same outputs, depth space included.
+// A view with depth positions (the line search's union lists) gets the render record alone, at the Gaussian's depth
+// position: one 64-B record per Gaussian, read in depth order by the union binning.
 template <bool RAW, bool STAGE>
 __global__ __launch_bounds__(256) void k_preprocess_views(PreViewsK pv, GaussK g) {
   extern __shared__ __attribute__((aligned(16))) float s_sh[];  // [256 * rest_stride] (STAGE)
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int64_t i0 = (int64_t)blockIdx.x * blockDim.x;
-  const int64_t i = i0 + tid;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = i < g.P;
   PreIn in{};
   if (live) load_pre_in<RAW>(g, i, in);
-  asm volatile("" : : "v"(in.x), "v"(in.y), "v"(in.z), "v"(in.c[0]), "v"(in.c[1]), "v"(in.c[2]), "v"(in.c[3]),
-               "v"(in.c[4]), "v"(in.c[5]), "v"(in.qw), "v"(in.op));
-  int64_t total = 0, n4 = 0;
-  if constexpr (STAGE) {
-    const int64_t nv = min((int64_t)blockDim.x, g.P - i0);
-    total = nv * g.rest_stride;
-    n4 = total / 4;
-    const float4* src4 = reinterpret_cast<const float4*>(g.rest + i0 * g.rest_stride);
-    float4* dst4 = reinterpret_cast<float4*>(s_sh);
-    for (int64_t c = w; c * 64 < n4; c += 4) {
-      const int64_t e = min(c * 64 + lane, n4 - 1);
-      glds16(src4 + e, dst4 + c * 64);
-    }
-  }
+  pin_pre_in(in);
+  ShSpan sp{};
+  if constexpr (STAGE) sp = stage_sh_dma_begin(g, 0, s_sh);
   // view 0's geometry while the rows land (as k_preprocess_dma)
   PreOut o0;
-  o0.depth = 0.f;
   const bool vis0 = live && preprocess_core<RAW, false>(pv.v[0], g, i, in, o0);
-  if constexpr (STAGE) {
-    __syncthreads();
-    if (n4 * 4 < total) {
-      for (int64_t e = n4 * 4 + tid; e < total; e += blockDim.x) s_sh[e] = g.rest[i0 * g.rest_stride + e];
-      __syncthreads();
-    }
-  }
+  if constexpr (STAGE) stage_sh_dma_finish(g, 0, s_sh, sp);
   if (!live) return;
-  if constexpr (STAGE) {
-    g.rest = s_sh;
-    g.rest_base = i0;
-  }
 #pragma unroll 1
   for (int b = 0; b < pv.n; ++b) {
     const ViewK& v = pv.v[b];
@@ -199,51 +204,27 @@ __global__ __launch_bounds__(256) void k_preprocess_views(PreViewsK pv, GaussK g
       o = o0;
       vis = vis0;
     } else {
-      o.depth = 0.f;
       vis = preprocess_core<RAW, false>(v, g, i, in, o);
     }
-    if (ob.pos) {
-      // depth space (the line search's union lists): the render record alone, at the Gaussian's depth position, its
-      // rect slot zero when culled -- one 64-B record per Gaussian, read in depth order by the union binning
-      float4* rec = ob.rec + RECS * (size_t)ob.pos[i];
-      if (vis) {
-        preprocess_color(v, g, i, in, o);
-        rec[0] = make_float4(o.x, o.y, o.conic[0], o.conic[1]);
-        rec[1] = make_float4(o.conic[2], o.opac, o.rgb[0], o.rgb[1]);
-        rec[2] = make_float4(o.rgb[2], 1.0f / o.depth, __uint_as_float(o.clamped), o.tq);
-        rec[3] = make_float4(__uint_as_float((uint32_t)o.rmin_x | ((uint32_t)o.rmin_y << 16)),
-                             __uint_as_float((uint32_t)o.rmax_x | ((uint32_t)o.rmax_y << 16)), 0.f, 0.f);
-      } else {
-        rec[3] = make_float4(0.f, 0.f, 0.f, 0.f);
-      }
+    float4* const drec = ob.pos ? ob.rec + RECS * (size_t)ob.pos[i] : nullptr;  // depth space
+    // (the culled exit stands before the colour: `if (vis)` around the colour and one writer call behind it compiled
+    // to 2-5 more VGPRs in every instantiation)
+    if (!vis) {
+      if (drec) write_culled_record(drec);
+      else write_index_outputs(ob, nullptr, i, false, o);
       continue;
     }
-    ob.tiles[i] = 0u;
-    ob.depth_key[i] = o.depth > 0.2f ? __float_as_uint(o.depth) : 0xFFFFFFFFu;
-    if (!vis) continue;
     preprocess_color(v, g, i, in, o);
-    float4* rec = ob.rec + RECS * i;
-    rec[0] = make_float4(o.x, o.y, o.conic[0], o.conic[1]);
-    rec[1] = make_float4(o.conic[2], o.opac, o.rgb[0], o.rgb[1]);
-    rec[2] = make_float4(o.rgb[2], 1.0f / o.depth, __uint_as_float(o.clamped), o.tq);
-    ob.tiles[i] = (uint32_t)((o.rmax_x - o.rmin_x) * (o.rmax_y - o.rmin_y));
-    const uint2 rc = make_uint2((uint32_t)o.rmin_x | ((uint32_t)o.rmin_y << 16), (uint32_t)o.rmax_x | ((uint32_t)o.rmax_y << 16));
-    ob.rect[i] = rc;
-    rec[3] = make_float4(__uint_as_float(rc.x), __uint_as_float(rc.y), 0.f, 0.f);
-    ob.clampw[i] = o.clamped;
+    if (drec) write_record(drec, o);
+    else write_index_outputs(ob, nullptr, i, true, o);
   }
 }
 
 // whether k_preprocess_views can stage the SH rows: raw GaussianModel leaves with the SH rest as its contiguous 16-B
-// aligned leaf (otherwise the unstaged instantiation runs; until round 5 a per-view launch_preprocess did, which
-// ignored the depth positions of the line search's union workspaces: ADVICE r04)
-static bool views_pass_ok(const GaussK& g) {
-  return g.raw && !g.colors && !g.cov3D && g.rest && g.M > 1 && g.rest_stride == 3 * (g.M - 1) &&
-         ((uintptr_t)g.rest & 15u) == 0;
-}
+// aligned leaf (otherwise the unstaged instantiation runs, depth positions included)
+static bool views_pass_ok(const GaussK& g) { return g.raw && !g.cov3D && stage_lead(g) == 0; }
 
-int launch_preprocess_views(const PreViewsK& pv, const GaussK& g, const GeomBufs* gbs, hipStream_t s) {
-  (void)gbs;
+int launch_preprocess_views(const PreViewsK& pv, const GaussK& g, hipStream_t s) {
   if (g.P == 0 || pv.n == 0) return GSLM_OK;
   const dim3 grid((unsigned)((g.P + 255) / 256));
   if (views_pass_ok(g)) {
@@ -1085,40 +1066,24 @@ int launch_union_binning(const ViewK& v, int64_t P, const GeomBufs& ug, const Bi
 
 // ------------------------------------------------------------------ launchers
 
-// k_preprocess_dma (default) or the register-staged k_preprocess: GSLM_PREPROCESS_STAGING=reg selects the latter
-// (an A/B switch; both write the bitwise same records)
-static const bool g_preprocess_dma = [] {
-  const char* e = getenv("GSLM_PREPROCESS_STAGING");
-  return !(e && e[0] == 'r');
-}();
-
-int launch_preprocess(const ViewK& v, const GaussK& g, const GeomBufs& gb, int* radii_out, hipStream_t s) {
-  if (g.P == 0) return GSLM_OK;
-  const int nb = (int)((g.P + 255) / 256);
-  // stage the SH rows through LDS: the contiguous [P, M-1, 3] rest leaf (raw GaussianModel tensors, or the dc / rest
-  // pair of render(separate_sh=True)), or the rest inside upstream's [P, M, 3] features tensor (render()'s
-  // get_features: each rest row 3 floats past its dc at one 3M stride) -- whole rows staged from the dc slot
+// The SH rows staged through LDS wherever stage_lead allows: the contiguous [P, M-1, 3] rest leaf (raw GaussianModel
+// tensors, or the dc / rest pair of render(separate_sh=True)), or the rest inside upstream's [P, M, 3] features tensor
+// (render()'s get_features: each rest row 3 floats past its dc at one 3M stride) -- whole rows staged from the dc slot.
+template <bool RAW>
+static void launch_preprocess_raw(const ViewK& v, const GaussK& g, const PreOutBufs& ob, int* radii_out, hipStream_t s) {
+  const dim3 grid((unsigned)((g.P + 255) / 256));
   const int lead = stage_lead(g);
-  const bool stage = lead >= 0;
-  const size_t lds = stage ? (size_t)256 * g.rest_stride * sizeof(float) : 0;
-  if (g.raw && stage && g_preprocess_dma)
-    hipLaunchKernelGGL((k_preprocess_dma<true>), dim3(nb), dim3(256), lds, s, v, g, gb.rec, gb.depth_key, gb.tiles,
-                       gb.rect, gb.clampw, radii_out, lead);
-  else if (stage && g_preprocess_dma)
-    hipLaunchKernelGGL((k_preprocess_dma<false>), dim3(nb), dim3(256), lds, s, v, g, gb.rec, gb.depth_key, gb.tiles,
-                       gb.rect, gb.clampw, radii_out, lead);
-  else if (g.raw && stage)
-    hipLaunchKernelGGL((k_preprocess<true, true>), dim3(nb), dim3(256), lds, s, v, g, gb.rec, gb.depth_key, gb.tiles,
-                       gb.rect, gb.clampw, radii_out, lead);
-  else if (g.raw)
-    hipLaunchKernelGGL((k_preprocess<true, false>), dim3(nb), dim3(256), 0, s, v, g, gb.rec, gb.depth_key, gb.tiles,
-                       gb.rect, gb.clampw, radii_out, lead);
-  else if (stage)
-    hipLaunchKernelGGL((k_preprocess<false, true>), dim3(nb), dim3(256), lds, s, v, g, gb.rec, gb.depth_key, gb.tiles,
-                       gb.rect, gb.clampw, radii_out, lead);
+  if (lead >= 0)
+    hipLaunchKernelGGL((k_preprocess_dma<RAW>), grid, dim3(256), (size_t)256 * g.rest_stride * sizeof(float), s, v, g, ob,
+                       radii_out, lead);
   else
-    hipLaunchKernelGGL((k_preprocess<false, false>), dim3(nb), dim3(256), 0, s, v, g, gb.rec, gb.depth_key, gb.tiles,
-                       gb.rect, gb.clampw, radii_out, lead);
+    hipLaunchKernelGGL((k_preprocess<RAW>), grid, dim3(256), 0, s, v, g, ob, radii_out);
+}
+
+int launch_preprocess(const ViewK& v, const GaussK& g, const PreOutBufs& ob, int* radii_out, hipStream_t s) {
+  if (g.P == 0) return GSLM_OK;
+  if (g.raw) launch_preprocess_raw<true>(v, g, ob, radii_out, s);
+  else launch_preprocess_raw<false>(v, g, ob, radii_out, s);
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
 }

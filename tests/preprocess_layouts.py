@@ -1,5 +1,4 @@
-"""Helper of tests/test_gpu_preprocess_records.py, tests/test_oracle_preprocess_records.py and tests/preprocess_worker.py
-(no tests here).
+"""Helper of tests/test_gpu_preprocess_records.py and tests/test_oracle_preprocess_records.py (no tests here).
 
   * the SH layouts a caller can hand to gslm_preprocess / gslm_preprocess_views, each holding the same float values, and
     stage_lead() (csrc/gslm_kernels.hpp) restated on their pointers and strides;
@@ -379,7 +378,7 @@ def gpu_record(parsed):
     return out
 
 
-# ------------------------------------------------------------------ every path of one case (GPU; the worker runs it too)
+# ------------------------------------------------------------------ every path of one case (GPU)
 def run_case(case, layouts=LAYOUTS, sizes=SIZES, raws=(True, False)):
     """{(P, view, raw, layout): run_preprocess's arrays} of one case of the branch scene, through gslm_preprocess."""
     model, cams, o32s, _ = oracle_case(case)

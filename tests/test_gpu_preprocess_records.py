@@ -1,5 +1,6 @@
-"""GPU: the render records of k_preprocess / k_preprocess_dma / k_preprocess_views (csrc/forward.hip) on every SH
-staging path and layout, against the float64 record and bitwise against each other.
+"""GPU: the render records of k_preprocess<RAW> (SH rows read from global memory), k_preprocess_dma<RAW> (staged by
+LDS-DMA) and k_preprocess_views<RAW, STAGE> (csrc/forward.hip) on every layout, against the float64 record and bitwise
+against each other.
 
 Scene: chain_jacobian.branch_case's model (P = 768, 64x48, two views; tan-FoV clamp, antialiasing clamp, SH clamps on
 every channel, 14 % culled), cut to the (allocated, active) degree pairs (3,3) (3,1) (3,0) (2,2) (1,1) (0,0) with plain
@@ -18,15 +19,12 @@ c. tq, the alpha threshold, from each record's own opacity: negative exactly whe
    [t - 1 ulp, t + 2 ulp] of t = 2 ln(255 o) 1.02 + 1e-4.
 d. The depth keys gslm_preprocess_views leaves: the float32 depth's bits for every Gaussian in front of the near plane,
    culled by its footprint or not, 0xFFFFFFFF otherwise.
-e. Every layout writes the bits of layout `leaf`.
+e. Every layout writes the bits of layout `leaf`: the LDS-DMA records (leaf, features) equal those of the layouts that
+   read global memory unstaged (leaf_shifted, features_shifted, padded).
 f. gslm_preprocess_views (staged and unstaged instantiations, index space and depth space) writes gslm_preprocess's bits.
-g. The register-staged kernels (GSLM_PREPROCESS_STAGING=reg, a fresh child process) write the LDS-DMA kernels' bits.
 h. The drop-in rasterizer's outputs, gradients and tangents do not depend on how the caller lays out the SH tensor.
 """
 import functools
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
@@ -36,7 +34,6 @@ import preprocess_layouts as pl
 from margins import record
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 DEV = "cuda"
 case_param = pytest.mark.parametrize("case", pl.CASES, ids=pl.case_id)
 
@@ -268,33 +265,6 @@ def test_preprocess_views_writes_the_bits_of_preprocess(case, nviews):
                     bad.append(f"{tag}: depth-space rect slot")
                 if not (rc[~v][:, 12:14].view(np.uint32) == 0).all():
                     bad.append(f"{tag}: depth-space rect slot of a culled Gaussian not zero")
-    assert not bad, (len(bad), bad[:12])
-
-
-# ------------------------------------------------------------------ g. the register-staged kernels
-def test_register_staged_kernels_write_the_same_bits(tmp_path):
-    """GSLM_PREPROCESS_STAGING=reg is read once when the library loads: one fresh child process runs k_preprocess<RAW,
-    true> on the (3, 3) and (2, 2) cases (leaf and features, both raw values, every size, both views); its arrays equal
-    this process's LDS-DMA results bit for bit."""
-    import preprocess_worker as pw
-    assert os.environ.get("GSLM_PREPROCESS_STAGING", "")[:1] != "r", "the parent must run the LDS-DMA kernels"
-    out = tmp_path / "reg.npz"
-    env = dict(os.environ, GSLM_PREPROCESS_STAGING="reg")
-    r = subprocess.run([sys.executable, os.path.join(HERE, "preprocess_worker.py"), str(out)], env=env,
-                       capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0, r.stderr[-3000:]
-    got = np.load(out)
-    bad, n = [], 0
-    for case in pw.WORKER_CASES:
-        res = _results(case)
-        for (P, b, raw, name), ref in res.items():
-            if name not in pw.WORKER_LAYOUTS:
-                continue
-            mine = {f: got[pw.key(case, P, b, raw, name, f)] for f in ("rec", "tiles", "rect", "clampw", "radii")}
-            v = _vis(ref)
-            bad += [f"{pl.case_id(case)} {name} raw={int(raw)} P={P} view {b}: {x}" for x in pl.same_bits(mine, ref, v)]
-            n += 1
-    assert n == 2 * len(pl.SIZES) * 2 * 2 * 2
     assert not bad, (len(bad), bad[:12])
 
 
