@@ -1,4 +1,5 @@
 // api.hip -- extern "C" entry points of libgslm.so (declared in include/gslm.h).
+#include <cmath>
 #include <cstring>
 #include <string>
 #include <vector>
@@ -327,6 +328,23 @@ __global__ void k_read_counts(CountPtrs c, int n, uint32_t* __restrict__ out) {
   const int k = threadIdx.x;
   if (k < n) out[k] = *c.p[k];
 }
+
+// gslm_robust as the entry points take it (gslm_kernels.hpp)
+int robust_arg(const gslm_robust* robust, const char* what, bool* on, gslm_robust* out) {
+  *on = false;
+  if (!robust || robust->kind == GSLM_ROBUST_NONE) return GSLM_OK;
+  if (robust->kind != GSLM_ROBUST_HUBER && robust->kind != GSLM_ROBUST_CAUCHY) {
+    set_error(std::string(what) + ": unknown robust kind (GSLM_ROBUST_NONE / HUBER / CAUCHY)");
+    return GSLM_ERR_INVALID;
+  }
+  if (!(std::isfinite(robust->delta) && robust->delta > 0.0f)) {
+    set_error(std::string(what) + ": robust delta must be finite and > 0");
+    return GSLM_ERR_INVALID;
+  }
+  *on = true;
+  *out = *robust;
+  return GSLM_OK;
+}
 }  // namespace gslm
 
 extern "C" {
@@ -389,12 +407,17 @@ size_t gslm_loss_scratch_bytes(int32_t H, int32_t W) {
   return (size_t)(ntiles > 0 ? ntiles : 1) * sizeof(double);
 }
 
-// gslm_rasterize_loss and its exposure form: one body, `exposure` NULL for the plain one
+// gslm_rasterize_loss and its exposure and robust forms: one body, `exposure` / `robust` NULL for the plain one
 static int rasterize_loss(const gslm_view* view, int64_t P, void* geom, void* binning, size_t binning_bytes, int64_t N,
                           const float* gt, const float* alpha_mask, const float* exposure, bool want_exposure,
-                          void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate, void* stream) {
+                          void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate, void* stream,
+                          const gslm_robust* robust = nullptr) {
+  bool rob = false;
+  gslm_robust rb{};
+  int st = robust_arg(robust, "rasterize_loss_robust", &rob, &rb);
+  if (st) return st;
   ViewK v;
-  int st = make_view(view, 1, &v);
+  st = make_view(view, 1, &v);
   if (st) return st;
   if (want_exposure && !exposure) { set_error("rasterize_loss_exposure: NULL exposure"); return GSLM_ERR_INVALID; }
   if (binning_bytes < gslm_binning_bytes(N, v.H, v.W)) { set_error("binning workspace too small"); return GSLM_ERR_CAPACITY; }
@@ -407,7 +430,15 @@ static int rasterize_loss(const gslm_view* view, int64_t P, void* geom, void* bi
   hipStream_t s = (hipStream_t)stream;
   if ((st = launch_binning(v, P, gb, bb, N, s))) return st;
   return launch_render_loss(v, gb, bb, gt, alpha_mask, (double*)scratch, loss_dev, accumulate ? 1 : 0, s, nullptr, 0,
-                            nullptr, exposure);
+                            nullptr, exposure, rob ? &rb : nullptr);
+}
+
+int gslm_rasterize_loss_robust(const gslm_view* view, int64_t P, void* geom, void* binning, size_t binning_bytes,
+                               int64_t N, const float* gt, const float* alpha_mask, const gslm_robust* robust,
+                               void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate,
+                               void* stream) {
+  return rasterize_loss(view, P, geom, binning, binning_bytes, N, gt, alpha_mask, nullptr, false, scratch,
+                        scratch_bytes, loss_dev, accumulate, stream, robust);
 }
 
 int gslm_rasterize_loss(const gslm_view* view, int64_t P, void* geom, void* binning, size_t binning_bytes, int64_t N,
@@ -532,9 +563,13 @@ static int rasterize_loss_slot(const gslm_view* view, int64_t P, const void* geo
                                const void* binning, size_t binning_bytes, int64_t N, int32_t slot, int32_t n_sets,
                                const float* gt, const float* alpha_mask, const float* exposure, bool want_exposure,
                                void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate,
-                               void* stream) {
+                               void* stream, const gslm_robust* robust = nullptr) {
+  bool rob = false;
+  gslm_robust rb{};
+  int st = robust_arg(robust, "rasterize_loss_slot_robust", &rob, &rb);
+  if (st) return st;
   ViewK v;
-  int st = make_view(view, 1, &v);
+  st = make_view(view, 1, &v);
   if (st) return st;
   if (want_exposure && !exposure) { set_error("rasterize_loss_slot_exposure: NULL exposure"); return GSLM_ERR_INVALID; }
   if (n_sets < 1 || n_sets > MAX_UNION_SETS || slot < 0 || slot >= n_sets) {
@@ -554,7 +589,17 @@ static int rasterize_loss_slot(const gslm_view* view, int64_t P, const void* geo
   bin_layout(N, v.gx * v.gy, const_cast<void*>(binning), &bb);
   union_masks_layout(N, v.gx * v.gy, const_cast<void*>(binning), &um);
   return launch_render_loss(v, gb, bb, gt, alpha_mask, (double*)scratch, loss_dev, accumulate ? 1 : 0,
-                            (hipStream_t)stream, N > 0 ? um.sorted : nullptr, 4 * slot, um.nsets, exposure);
+                            (hipStream_t)stream, N > 0 ? um.sorted : nullptr, 4 * slot, um.nsets, exposure,
+                            rob ? &rb : nullptr);
+}
+
+int gslm_rasterize_loss_slot_robust(const gslm_view* view, int64_t P, const void* geom, size_t set_bytes,
+                                    const void* binning, size_t binning_bytes, int64_t N, int32_t slot,
+                                    int32_t n_sets, const float* gt, const float* alpha_mask,
+                                    const gslm_robust* robust, void* scratch, size_t scratch_bytes, double* loss_dev,
+                                    int32_t accumulate, void* stream) {
+  return rasterize_loss_slot(view, P, geom, set_bytes, binning, binning_bytes, N, slot, n_sets, gt, alpha_mask, nullptr,
+                             false, scratch, scratch_bytes, loss_dev, accumulate, stream, robust);
 }
 
 int gslm_rasterize_loss_slot(const gslm_view* view, int64_t P, const void* geom, size_t set_bytes, const void* binning,
@@ -582,9 +627,13 @@ static int rasterize_loss_sets(const gslm_view* view, int64_t P, const void* con
                                int32_t first_set, size_t set_bytes, const void* binning, size_t binning_bytes,
                                int64_t N, const float* gt, const float* alpha_mask, const float* const* exposure,
                                bool want_exposure, void* scratch, size_t scratch_bytes, double* const* loss_dev,
-                               int32_t accumulate, void* stream) {
+                               int32_t accumulate, void* stream, const gslm_robust* robust = nullptr) {
+  bool rob = false;
+  gslm_robust rb{};
+  int st = robust_arg(robust, "rasterize_loss_sets_robust", &rob, &rb);
+  if (st) return st;
   ViewK v;
-  int st = make_view(view, 1, &v);
+  st = make_view(view, 1, &v);
   if (st) return st;
   if (n < 1 || first_set < 0 || first_set + n > MAX_UNION_SETS) {
     set_error("rasterize_loss_sets: 1 <= n parameter sets, slots first_set .. first_set + n - 1 within [0, 8)");
@@ -616,7 +665,17 @@ static int rasterize_loss_sets(const gslm_view* view, int64_t P, const void* con
   union_masks_layout(N, v.gx * v.gy, const_cast<void*>(binning), &um);
   // um.nsets: slots at or past the set count gslm_union_binning recorded render a NaN loss (as the slot form)
   return launch_render_loss_sets(v, sr, n, bb, um.sorted, gt, alpha_mask, (double*)scratch, lp, accumulate ? 1 : 0,
-                                 (hipStream_t)stream, first_set, um.nsets, want_exposure ? &xp : nullptr);
+                                 (hipStream_t)stream, first_set, um.nsets, want_exposure ? &xp : nullptr,
+                                 rob ? &rb : nullptr);
+}
+
+int gslm_rasterize_loss_sets_robust(const gslm_view* view, int64_t P, const void* const* geoms, int32_t n,
+                                    int32_t first_set, size_t set_bytes, const void* binning, size_t binning_bytes,
+                                    int64_t N, const float* gt, const float* alpha_mask, const gslm_robust* robust,
+                                    void* scratch, size_t scratch_bytes, double* const* loss_dev, int32_t accumulate,
+                                    void* stream) {
+  return rasterize_loss_sets(view, P, geoms, n, first_set, set_bytes, binning, binning_bytes, N, gt, alpha_mask, nullptr,
+                             false, scratch, scratch_bytes, loss_dev, accumulate, stream, robust);
 }
 
 int gslm_rasterize_loss_sets(const gslm_view* view, int64_t P, const void* const* geoms, int32_t n, int32_t first_set,

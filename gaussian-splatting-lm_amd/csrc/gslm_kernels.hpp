@@ -517,12 +517,53 @@ int launch_active_list(int64_t P, int64_t N, const GeomBufs& gb, const ScratchBu
                        uint32_t* scan_tmp, uint32_t* total, int32_t* ids, uint32_t* hrow, int64_t* count,
                        hipStream_t s);
 int launch_point_ids(const uint32_t* point_list, int64_t N, uint32_t* out, hipStream_t s);
+// ---- robust losses (gslm_robust, include/gslm.h): the two device functions both epilogues share -- the residual's
+// (residual.hip: rho' on the weight and the seed, rho in the loss) and the loss blends' (render_fwd.hip: rho alone).
+// One float test per element, fabsf(r) <= delta, decides the branch for rho' and for rho alike.  Every operation is
+// written out for a float32 restatement to follow bit by bit whatever the file is compiled with: no product is
+// contracted into the sum it feeds (the pragma names that choice: separate operations), and the float divisions are
+// taken in double and rounded once to float -- 53 bits are more than 2 x 24 + 2, so that is the correctly rounded
+// float quotient, also in a file that relaxes the float division (2.5 ulp without the correctly-rounded-divide flag).
+// A NaN r fails the test and comes out of either branch as NaN.
+__device__ __forceinline__ bool robust_inlier(float r, float delta) { return fabsf(r) <= delta; }
+
+__device__ __forceinline__ float div_rn(float a, float b) { return (float)((double)a / (double)b); }
+
+// rho'(r^2), float.  HUBER: 1 inside, delta / |r| outside.  CAUCHY: 1 / (1 + t t), t = r / delta.
+__device__ __forceinline__ float robust_weight(const gslm_robust rb, float r) {
+#pragma clang fp contract(off)
+  if (rb.kind == GSLM_ROBUST_HUBER) return robust_inlier(r, rb.delta) ? 1.0f : div_rn(rb.delta, fabsf(r));
+  const float t = div_rn(r, rb.delta);
+  const float tt = t * t;  // rounded on its own, then added
+  return div_rn(1.0f, 1.0f + tt);
+}
+
+// rho(r^2), double, from rd = (double)r and dd = (double)delta.  HUBER: rd rd inside, 2 dd |rd| - dd dd outside.
+// CAUCHY: dd dd log1p((rd / dd)^2).
+__device__ __forceinline__ double robust_rho(const gslm_robust rb, float r) {
+#pragma clang fp contract(off)
+  const double rd = (double)r, dd = (double)rb.delta;
+  if (rb.kind == GSLM_ROBUST_HUBER) {
+    if (robust_inlier(r, rb.delta)) return rd * rd;
+    const double a = (2.0 * dd) * fabs(rd), b = dd * dd;  // two rounded products, then their difference
+    return a - b;
+  }
+  const double q = rd / dd;
+  return (dd * dd) * log1p(q * q);
+}
+
+// gslm_robust as the entry points take it: NULL or kind NONE -> *on = false (the plain kernels run); an unknown kind or
+// a delta that is not finite and > 0 -> GSLM_ERR_INVALID with the error set (api.hip)
+int robust_arg(const gslm_robust* robust, const char* what, bool* on, gslm_robust* out);
+
 // amask (or NULL): the blend visits by the union list's per-set masks (bits `shift` .. shift + 3 of amask[k],
 // k_duplicate_union) with the records of gb (that set's geometry) instead of the point list's own quadrant bits;
-// exposure (or NULL): the camera's 12 device floats, applied to the final colour before the clamp
+// exposure (or NULL): the camera's 12 device floats, applied to the final colour before the clamp;
+// robust (or NULL; never with exposure): a checked HUBER / CAUCHY block, the per-tile sum then takes robust_rho
 int launch_render_loss(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const float* gt, const float* mask,
                        double* part, double* loss, int accumulate, hipStream_t s, const uint32_t* amask = nullptr,
-                       int shift = 0, const uint32_t* nsets = nullptr, const float* exposure = nullptr);
+                       int shift = 0, const uint32_t* nsets = nullptr, const float* exposure = nullptr,
+                       const gslm_robust* robust = nullptr);
 // ---- the line search's shared binning (forward.hip, gslm_union_*) ----
 constexpr int MAX_UNION_SETS = 8;  // 4 mask bits per set in one uint32 per list entry
 struct UnionSets {
@@ -554,7 +595,7 @@ struct ExpPtrsK {  // per set: its exposure map, 12 device floats (gslm_rasteriz
 int launch_render_loss_sets(const ViewK& v, const SetRecsK& sr, int nsets, const BinBufs& bb, const uint32_t* amask,
                             const float* gt, const float* mask, double* part, const LossPtrsK& lp, int accumulate,
                             hipStream_t s, int first_set = 0, const uint32_t* nsets_dev = nullptr,
-                            const ExpPtrsK* xp = nullptr);
+                            const ExpPtrsK* xp = nullptr, const gslm_robust* robust = nullptr);
 int launch_union_rect(int64_t P, const UnionSets& u, const GeomBufs& ug, hipStream_t s);
 int launch_depth_positions(int64_t P, const uint32_t* order, uint32_t* pos, hipStream_t s);
 int launch_union_binning(const ViewK& v, int64_t P, const GeomBufs& ug, const BinBufs& bb, const UnionMasks& um,

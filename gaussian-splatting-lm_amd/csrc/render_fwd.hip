@@ -26,7 +26,10 @@ enum { FWD_FULL = 0, FWD_NO_INV = 1, FWD_LOSS = 2 };
 // EXPO (FWD_LOSS only): the trained exposure's loss (gslm_rasterize_loss_exposure) -- the pixel's final colour goes
 // through the camera's 3x4 affine map X (12 device floats, wave-uniform) before the clamp, k_lm_residual_exposure's
 // arithmetic in its order.  X is read after the blend loop, which is the same loop with the same registers.
-template <int MODE, bool SLOT = false, bool EXPO = false>
+// ROBUST (FWD_LOSS only, never with EXPO): the robust loss of the line search (gslm_rasterize_loss_robust) -- the
+// per-tile sum takes robust_rho(rb, r), k_lm_residual<true>'s expression on the same float r, in place of r^2; rb is
+// read in the epilogue alone, after the same blend loop.
+template <int MODE, bool SLOT = false, bool EXPO = false, bool ROBUST = false>
 __global__ __launch_bounds__(256) void k_render_fwd_wave(ViewK v, const uint2* __restrict__ ranges,
                                                           const uint32_t* __restrict__ tile_order,
                                                           const uint32_t* __restrict__ point_list,
@@ -35,8 +38,10 @@ __global__ __launch_bounds__(256) void k_render_fwd_wave(ViewK v, const uint2* _
                                                           uint32_t* __restrict__ n_contrib, const float* __restrict__ gt,
                                                           const float* __restrict__ mask, double* __restrict__ part,
                                                           const uint32_t* __restrict__ amask = nullptr, int shift = 0,
-                                                          const float* __restrict__ X = nullptr) {
+                                                          const float* __restrict__ X = nullptr,
+                                                          gslm_robust rb = gslm_robust{}) {
   static_assert(!EXPO || MODE == FWD_LOSS, "the exposure map belongs to the loss epilogue");
+  static_assert(!ROBUST || (MODE == FWD_LOSS && !EXPO), "the robust loss belongs to the plain loss epilogue");
   __shared__ float4 s_rec[4][3 * 64];
   const int tile = (int)tile_order[blockIdx.x];
   const int tile_x = tile % v.gx, tile_y = tile / v.gx;
@@ -122,7 +127,8 @@ __global__ __launch_bounds__(256) void k_render_fwd_wave(ViewK v, const uint2* _
         // a lane outside the image never gets here: with an offset column its exposed colour would not be 0
         const float Cc = EXPO ? ((R[0] * x[c] + R[1] * x[4 + c]) + R[2] * x[8 + c]) + x[4 * c + 3] : R[c];
         const float r = m * clamp01(Cc) - gt[c * HW + pid];
-        acc += (double)r * (double)r;
+        if constexpr (ROBUST) acc += robust_rho(rb, r);
+        else acc += (double)r * (double)r;
       }
     }
 #pragma unroll
@@ -148,13 +154,16 @@ __global__ __launch_bounds__(256) void k_render_fwd_wave(ViewK v, const uint2* _
 // Every set's visits and their order are the single-set kernel's: the same losses, bitwise.
 // EXPO: set a's final colour goes through its own exposure map xp.x[a] (k_render_fwd_wave's EXPO epilogue), read
 // after the list walk and indexed by the unrolled set number only.
-template <int NS, bool EXPO = false>
+// ROBUST (never with EXPO): every set's per-tile sum takes robust_rho(rb, r) in place of r^2 (one block for all sets).
+template <int NS, bool EXPO = false, bool ROBUST = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS <= 6 ? 8 : 1))) void k_render_loss_sets(ViewK v, const uint2* __restrict__ ranges,
                                                            const uint32_t* __restrict__ tile_order,
                                                            const uint32_t* __restrict__ point_list,
                                                            const uint32_t* __restrict__ amask, SetRecsK sr,
                                                            const float* __restrict__ gt, const float* __restrict__ mask,
-                                                           double* __restrict__ part, int shift, ExpPtrsK xp) {
+                                                           double* __restrict__ part, int shift, ExpPtrsK xp,
+                                                           gslm_robust rb) {
+  static_assert(!ROBUST || !EXPO, "the robust loss belongs to the plain loss epilogue");
   __shared__ float4 s_rec[4][3 * 64];
   const int tile = (int)tile_order[blockIdx.x];
   const int tile_x = tile % v.gx, tile_y = tile / v.gx;
@@ -270,7 +279,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NS <= 6 ? 8
       for (int c = 0; c < 3; ++c) {
         const float Cc = EXPO ? ((R[0] * x[c] + R[1] * x[4 + c]) + R[2] * x[8 + c]) + x[4 * c + 3] : R[c];
         const float r = mv * clamp01(Cc) - gtc[c];
-        acc += (double)r * (double)r;
+        if constexpr (ROBUST) acc += robust_rho(rb, r);
+        else acc += (double)r * (double)r;
       }
     }
 #pragma unroll
@@ -304,7 +314,8 @@ __global__ __launch_bounds__(256) void k_tile_loss_final_sets(const double* __re
 
 int launch_render_loss_sets(const ViewK& v, const SetRecsK& sr, int nsets, const BinBufs& bb, const uint32_t* amask,
                             const float* gt, const float* mask, double* part, const LossPtrsK& lp, int accumulate,
-                            hipStream_t s, int first_set, const uint32_t* nsets_dev, const ExpPtrsK* xp) {
+                            hipStream_t s, int first_set, const uint32_t* nsets_dev, const ExpPtrsK* xp,
+                            const gslm_robust* robust) {
   const int ntiles = v.gx * v.gy;
   if (ntiles == 0) {
     if (!accumulate)
@@ -313,15 +324,23 @@ int launch_render_loss_sets(const ViewK& v, const SetRecsK& sr, int nsets, const
   }
   const dim3 grid(ntiles), block(TILE_PIX);
   const ExpPtrsK x = xp ? *xp : ExpPtrsK{};
+  const gslm_robust rb = robust ? *robust : gslm_robust{};
+  if (xp && robust) {
+    set_error("rasterize_loss_sets: no exposure x robust form");
+    return GSLM_ERR_INVALID;
+  }
   switch (nsets) {
 #define GSLM_LOSS_SETS(NS)                                                                                          \
   case NS:                                                                                                          \
     if (xp)                                                                                                         \
       hipLaunchKernelGGL((k_render_loss_sets<NS, true>), grid, block, 0, s, v, bb.ranges, bb.tile_order,            \
-                         bb.point_list, amask, sr, gt, mask, part, 4 * first_set, x);                               \
+                         bb.point_list, amask, sr, gt, mask, part, 4 * first_set, x, rb);                           \
+    else if (robust)                                                                                                \
+      hipLaunchKernelGGL((k_render_loss_sets<NS, false, true>), grid, block, 0, s, v, bb.ranges, bb.tile_order,     \
+                         bb.point_list, amask, sr, gt, mask, part, 4 * first_set, x, rb);                           \
     else                                                                                                            \
       hipLaunchKernelGGL((k_render_loss_sets<NS, false>), grid, block, 0, s, v, bb.ranges, bb.tile_order,           \
-                         bb.point_list, amask, sr, gt, mask, part, 4 * first_set, x);                               \
+                         bb.point_list, amask, sr, gt, mask, part, 4 * first_set, x, rb);                           \
     break;
     GSLM_LOSS_SETS(1) GSLM_LOSS_SETS(2) GSLM_LOSS_SETS(3) GSLM_LOSS_SETS(4)
     GSLM_LOSS_SETS(5) GSLM_LOSS_SETS(6) GSLM_LOSS_SETS(7) GSLM_LOSS_SETS(8)
@@ -372,13 +391,27 @@ int launch_render_fwd(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, con
 
 int launch_render_loss(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const float* gt, const float* mask,
                        double* part, double* loss, int accumulate, hipStream_t s, const uint32_t* amask, int shift,
-                       const uint32_t* nsets, const float* exposure) {
+                       const uint32_t* nsets, const float* exposure, const gslm_robust* robust) {
   const int ntiles = v.gx * v.gy;
   if (ntiles == 0) {
     if (!accumulate) GSLM_HIP_CHECK(hipMemsetAsync(loss, 0, sizeof(double), s));
     return GSLM_OK;
   }
-  if (exposure && amask)
+  if (exposure && robust) {
+    set_error("rasterize_loss: no exposure x robust form");
+    return GSLM_ERR_INVALID;
+  }
+  if (robust && amask)
+    hipLaunchKernelGGL((k_render_fwd_wave<FWD_LOSS, true, false, true>), dim3(ntiles), dim3(TILE_PIX), 0, s, v,
+                       bb.ranges, bb.tile_order, bb.point_list, gb.rec, (float*)nullptr, (float*)nullptr,
+                       (float*)nullptr, (uint32_t*)nullptr, gt, mask, part, amask, shift, (const float*)nullptr,
+                       *robust);
+  else if (robust)
+    hipLaunchKernelGGL((k_render_fwd_wave<FWD_LOSS, false, false, true>), dim3(ntiles), dim3(TILE_PIX), 0, s, v,
+                       bb.ranges, bb.tile_order, bb.point_list, gb.rec, (float*)nullptr, (float*)nullptr,
+                       (float*)nullptr, (uint32_t*)nullptr, gt, mask, part, (const uint32_t*)nullptr, 0,
+                       (const float*)nullptr, *robust);
+  else if (exposure && amask)
     hipLaunchKernelGGL((k_render_fwd_wave<FWD_LOSS, true, true>), dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges,
                        bb.tile_order, bb.point_list, gb.rec, (float*)nullptr, (float*)nullptr, (float*)nullptr,
                        (uint32_t*)nullptr, gt, mask, part, amask, shift, exposure);

@@ -16,17 +16,22 @@
 // operation, so r, w and seed are bit-identical to it.
 #include <algorithm>
 
-#include "gslm_internal.hpp"
+#include "gslm_kernels.hpp"
 
 namespace gslm {
 
 constexpr int RES_THREADS = 256;
 
+// ROBUST (gslm_lm_residual_robust; rb a checked HUBER / CAUCHY block, robust_weight / robust_rho of gslm_kernels.hpp):
+//   w = ((m m) inside) rho',   seed = (((-2 m) inside) r) rho',   loss += 2 sum rho     -- r itself is stored unscaled.
+// The plain instantiation reads no rb and is the kernel it was.
+template <bool ROBUST>
 __global__ __launch_bounds__(RES_THREADS) void k_lm_residual(int64_t HW, const float* __restrict__ color,
                                                              const float* __restrict__ gt,
                                                              const float* __restrict__ mask,
                                                              float* __restrict__ residual, float* __restrict__ weight,
-                                                             float* __restrict__ seed, double* __restrict__ part) {
+                                                             float* __restrict__ seed, double* __restrict__ part,
+                                                             gslm_robust rb) {
   __shared__ double s[RES_THREADS / 64];
   double acc = 0.0;
   const int64_t stride = (int64_t)gridDim.x * RES_THREADS;
@@ -39,9 +44,16 @@ __global__ __launch_bounds__(RES_THREADS) void k_lm_residual(int64_t HW, const f
       const float inside = (R >= 0.0f && R <= 1.0f) ? 1.0f : 0.0f;
       const float r = m * clamp01(R) - gt[k];
       if (residual) residual[k] = r;
-      if (weight) weight[k] = (m * m) * inside;
-      if (seed) seed[k] = ((-2.0f * m) * inside) * r;
-      acc += (double)r * (double)r;
+      if constexpr (ROBUST) {
+        const float dr = robust_weight(rb, r);
+        if (weight) weight[k] = ((m * m) * inside) * dr;
+        if (seed) seed[k] = (((-2.0f * m) * inside) * r) * dr;
+        acc += robust_rho(rb, r);
+      } else {
+        if (weight) weight[k] = (m * m) * inside;
+        if (seed) seed[k] = ((-2.0f * m) * inside) * r;
+        acc += (double)r * (double)r;
+      }
     }
   }
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -232,9 +244,13 @@ size_t gslm_residual_scratch_bytes(int32_t H, int32_t W) {
   return (size_t)1024 * sizeof(double);
 }
 
-int gslm_lm_residual(int32_t H, int32_t W, const float* color, const float* gt, const float* alpha_mask,
-                     float* residual, float* weight, float* seed, void* scratch, size_t scratch_bytes,
-                     double* loss_dev, int32_t accumulate, void* stream) {
+// gslm_lm_residual and its robust form: one body, `robust` NULL for the plain one
+static int lm_residual(int32_t H, int32_t W, const float* color, const float* gt, const float* alpha_mask,
+                       const gslm_robust* robust, float* residual, float* weight, float* seed, void* scratch,
+                       size_t scratch_bytes, double* loss_dev, int32_t accumulate, void* stream) {
+  bool on = false;
+  gslm_robust rb{};
+  if (int st = robust_arg(robust, "lm_residual_robust", &on, &rb)) return st;
   if (H < 0 || W < 0) { set_error("lm_residual: negative image size"); return GSLM_ERR_INVALID; }
   const int64_t HW = (int64_t)H * W;
   if (HW > 0 && (!color || !gt)) { set_error("lm_residual: NULL color / gt"); return GSLM_ERR_INVALID; }
@@ -243,12 +259,30 @@ int gslm_lm_residual(int32_t H, int32_t W, const float* color, const float* gt, 
   hipStream_t s = (hipStream_t)stream;
   const int nb = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (HW + RES_THREADS - 1) / RES_THREADS));
   double* part = (double*)scratch;
-  hipLaunchKernelGGL(k_lm_residual, dim3(nb), dim3(RES_THREADS), 0, s, HW, color, gt, alpha_mask, residual, weight,
-                     seed, part);
+  if (on)
+    hipLaunchKernelGGL(k_lm_residual<true>, dim3(nb), dim3(RES_THREADS), 0, s, HW, color, gt, alpha_mask, residual,
+                       weight, seed, part, rb);
+  else
+    hipLaunchKernelGGL(k_lm_residual<false>, dim3(nb), dim3(RES_THREADS), 0, s, HW, color, gt, alpha_mask, residual,
+                       weight, seed, part, rb);
   GSLM_LAUNCH_CHECK();
   hipLaunchKernelGGL(k_lm_loss_final, dim3(1), dim3(RES_THREADS), 0, s, part, nb, accumulate ? 1 : 0, loss_dev);
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
+}
+
+int gslm_lm_residual(int32_t H, int32_t W, const float* color, const float* gt, const float* alpha_mask,
+                     float* residual, float* weight, float* seed, void* scratch, size_t scratch_bytes,
+                     double* loss_dev, int32_t accumulate, void* stream) {
+  return lm_residual(H, W, color, gt, alpha_mask, nullptr, residual, weight, seed, scratch, scratch_bytes, loss_dev,
+                     accumulate, stream);
+}
+
+int gslm_lm_residual_robust(int32_t H, int32_t W, const float* color, const float* gt, const float* alpha_mask,
+                            const gslm_robust* robust, float* residual, float* weight, float* seed, void* scratch,
+                            size_t scratch_bytes, double* loss_dev, int32_t accumulate, void* stream) {
+  return lm_residual(H, W, color, gt, alpha_mask, robust, residual, weight, seed, scratch, scratch_bytes, loss_dev,
+                     accumulate, stream);
 }
 
 

@@ -100,6 +100,14 @@ class GslmMatvecOptsDamp(ctypes.Structure):
     _fields_ = [("base", GslmMatvecOpts), ("damp_vec", ctypes.c_void_p)]
 
 
+class GslmRobust(ctypes.Structure):
+    """gslm_robust: a robust loss of the LM step, {kind, delta}."""
+    _fields_ = [("kind", ctypes.c_int32), ("delta", ctypes.c_float)]
+
+
+GSLM_ROBUST_NONE, GSLM_ROBUST_HUBER, GSLM_ROBUST_CAUCHY = 0, 1, 2
+
+
 class GslmViewWs(ctypes.Structure):
     """gslm_view_ws: one view's workspaces for gslm_gather_views."""
     _fields_ = [
@@ -194,6 +202,25 @@ EXPORTS = {
                                                          ctypes.c_void_p, ctypes.c_size_t,
                                                          ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
                                                          ctypes.c_void_p]),
+    # the loss blends under a robust loss: the plain forms with `robust` (a gslm_robust, by address) after alpha_mask
+    "gslm_rasterize_loss_robust": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int64, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p,
+                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t,
+                                                  ctypes.c_void_p, ctypes.c_int32, ctypes.c_void_p]),
+    "gslm_rasterize_loss_slot_robust": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int64, ctypes.c_void_p,
+                                                       ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t,
+                                                       ctypes.c_int64, ctypes.c_int32, ctypes.c_int32,
+                                                       ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                                       ctypes.c_int32, ctypes.c_void_p]),
+    "gslm_rasterize_loss_sets_robust": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int64,
+                                                       ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
+                                                       ctypes.c_int32, ctypes.c_size_t, ctypes.c_void_p,
+                                                       ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_void_p,
+                                                       ctypes.c_void_p, ctypes.c_size_t,
+                                                       ctypes.POINTER(ctypes.c_void_p), ctypes.c_int32,
+                                                       ctypes.c_void_p]),
     "gslm_forward": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.POINTER(GslmGaussians), ctypes.c_void_p,
                                     ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                     ctypes.c_size_t, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
@@ -330,6 +357,10 @@ EXPORTS = {
                                         ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                         ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int32,
                                         ctypes.c_void_p]),
+    "gslm_lm_residual_robust": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                               ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                               ctypes.c_int32, ctypes.c_void_p]),
     "gslm_exposure_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
     "gslm_lm_residual_exposure": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

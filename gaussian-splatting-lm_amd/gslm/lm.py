@@ -289,12 +289,33 @@ def _exposure_index(model, cams):
     return [int(model.exposure_mapping[c.image_name]) for c in cams]
 
 
+_ROBUST_KINDS = {"huber": _lib.GSLM_ROBUST_HUBER, "cauchy": _lib.GSLM_ROBUST_CAUCHY}
+
+
+def robust_option(robust):
+    """The `robust` option of LMProblem, LossEvaluator and lm_step checked: None, or (kind, delta) with kind "huber" or
+    "cauchy" and delta a finite number > 0 -- returned as None or the pair (kind, float(delta)); ValueError otherwise."""
+    if robust is None:
+        return None
+    ok = isinstance(robust, (tuple, list)) and len(robust) == 2 and isinstance(robust[0], str) \
+        and robust[0] in _ROBUST_KINDS and isinstance(robust[1], (int, float)) and not isinstance(robust[1], bool)
+    if not ok or not (math.isfinite(robust[1]) and robust[1] > 0):
+        raise ValueError(f"robust must be None, ('huber', delta) or ('cauchy', delta) with a finite delta > 0, "
+                         f"got {robust!r}")
+    return (robust[0], float(robust[1]))
+
+
+def _robust_struct(robust):
+    """The gslm_robust block of a checked option (None: no block)."""
+    return None if robust is None else _lib.GslmRobust(_ROBUST_KINDS[robust[0]], robust[1])
+
+
 class LMProblem(_ProductOpts):
     """The LM normal equations of one camera batch (one LM step's worth of cached geometry)."""
 
     def __init__(self, model, cams, bg, gts=None, alpha_masks=None, mask_xyz=True, damp=None, device="cuda",
                  ssim=False, lambda_dssim=0.2, sh_projection=False, train_exposure=False, damping="fixed",
-                 marquardt_floor=0.0):
+                 marquardt_floor=0.0, robust=None):
         """ssim=False: the residual train_jvp.py uses (disable_ssim=True, [r; r]); ssim=True: the
         [r1; r2] residual with the SSIM term (batch_training_loss.py:18-30, gslm_ssim_*).
 
@@ -322,7 +343,22 @@ class LMProblem(_ProductOpts):
         xyz and the exposure tail have no column in J: their d is lambda marquardt_floor, their right-hand side is
         zero and the iterates stay zero there.  The plain residual on the LM rows only: ValueError with ssim,
         train_exposure, mask_xyz=False, or the batched problem.  The lean CG loop does not run under it.
-        set_damping_vector / damping_vector: a caller-supplied per-element D >= 0 in place of either."""
+        set_damping_vector / damping_vector: a caller-supplied per-element D >= 0 in place of either.
+
+        robust: None, ("huber", delta) or ("cauchy", delta) -- the loss is 2 sum rho(r^2) over the residual elements
+        (Huber: r^2 where |r| <= delta, 2 delta |r| - delta^2 elsewhere; Cauchy: delta^2 log1p(r^2 / delta^2)), solved by
+        iteratively reweighted least squares in the first-order Triggs form: evaluate() multiplies weights[b] and
+        seeds[b] by rho'(r^2) at the linearisation point (gslm_lm_residual_robust) and `loss` is the robust loss, so
+        rhs() is -1/2 grad loss, the products are 2 J^T (W rho') J + D and every consumer -- the active list, the lean
+        loop, diagonal, cgls_jacobi, Marquardt damping, the batched problem and its union list -- runs unchanged;
+        residuals[b] stay raw.  The plain residual on the LM rows only: ValueError with ssim, train_exposure or
+        mask_xyz=False, and for anything that is not one of the three forms.  cgls_residual, which iterates on the raw
+        residuals, refuses a robust problem."""
+        self.robust = robust_option(robust)
+        if self.robust is not None and (ssim or train_exposure or not mask_xyz):
+            raise ValueError("robust runs the [r; r] residual on the LM rows (mask_xyz=True, no SSIM, no trained "
+                             "exposure)")
+        self._robust = _robust_struct(self.robust)
         if damping not in ("fixed", "marquardt"):
             raise ValueError(f"damping must be 'fixed' or 'marquardt', got {damping!r}")
         self.damping = damping
@@ -396,7 +432,8 @@ class LMProblem(_ProductOpts):
     # -------------------------------------------------------------- residual (A8)
     def evaluate(self):
         """Primal forward of every view; residuals, per-pixel weights and the J^T b seeds from one fused
-        epilogue per view (gslm_lm_residual); loss = 2 sum ||r||^2 (device double)."""
+        epilogue per view (gslm_lm_residual); loss = 2 sum ||r||^2 (device double).  With `robust` the epilogue is
+        gslm_lm_residual_robust: loss = 2 sum rho(r^2), weights and seeds times rho'."""
         live_masks()  # (a bad GSLM_LIVE_MASKS is refused before the geometry's row map reads it)
         if self.damping == "marquardt":
             self._dvec = None  # (the diagonal of the new weights: rebuilt on first use)
@@ -442,6 +479,13 @@ class LMProblem(_ProductOpts):
                     self._exp_rhs.data_ptr() + 48 * self.exp_idx[b], self._exp_scratch.data_ptr(),
                     self._exp_scratch.numel() * 8, loss.data_ptr(), int(b > 0), self.stream),
                     "gslm_lm_residual_exposure")
+                continue
+            if self._robust is not None:
+                check(lib.gslm_lm_residual_robust(
+                    vr.H, vr.W, R.data_ptr(), gt.data_ptr(), None if m is None else m.data_ptr(),
+                    ctypes.byref(self._robust), self.residuals[b].data_ptr(), self.weights[b].data_ptr(),
+                    self.seeds[b].data_ptr(), self.res_scratch.data_ptr(), self.res_scratch.numel() * 8,
+                    loss.data_ptr(), int(b > 0), self.stream), "gslm_lm_residual_robust")
                 continue
             check(lib.gslm_lm_residual(vr.H, vr.W, R.data_ptr(), gt.data_ptr(), None if m is None else m.data_ptr(),
                                        self.residuals[b].data_ptr(), self.weights[b].data_ptr(),
@@ -987,7 +1031,7 @@ class BatchedLMProblem(LMProblem, _StageTimes):
 
     def __init__(self, model, cams, bg, gts=None, alpha_masks=None, mask_xyz=True, damp=None, device="cuda",
                  ssim=False, lambda_dssim=0.2, sh_projection=False, union_active=False, damping="fixed",
-                 marquardt_floor=0.0):
+                 marquardt_floor=0.0, robust=None):
         if damping != "fixed" or marquardt_floor != 0.0:
             raise ValueError("BatchedLMProblem runs the fixed damping (damping='marquardt' is LMProblem's)")
         if not mask_xyz:
@@ -999,7 +1043,7 @@ class BatchedLMProblem(LMProblem, _StageTimes):
         if sh_projection not in (False, None, "auto"):
             raise ValueError("sh_projection is LMProblem's single-view mode; the batch carries SH-rest coordinates")
         super().__init__(model, cams, bg, gts=gts, alpha_masks=alpha_masks, mask_xyz=True, damp=damp, device=device,
-                         ssim=False, lambda_dssim=lambda_dssim, sh_projection=False)
+                         ssim=False, lambda_dssim=lambda_dssim, sh_projection=False, robust=robust)
         full = self.full_layout
         P, K, V = full.P, full.K, len(cams)
         self.rest_views = V if (K > 1 and V <= _lib.GSLM_MAX_REST_VIEWS and 3 * V < 3 * (K - 1)
@@ -1621,6 +1665,9 @@ def cgls_residual(prob, max_iter=10, restart_iter=10, tol=1e-10, atol=0.0, verbo
         raise ValueError("cgls_residual: the seven damping constants only (no damping vector)")
     if getattr(prob, "train_exposure", False):
         raise ValueError("cgls_residual: the residual-space recursion does not carry trained exposure")
+    if getattr(prob, "robust", None) is not None:
+        raise ValueError("cgls_residual: the recursion iterates on the raw residuals, not a robust problem's "
+                         "reweighted ones (cgls_fused / cgls_jacobi)")
     dev = prob.device
     rm = prob.residual_masks()
     b = [-r for r in prob.residuals]  # b = -[r; r]: one copy per view
@@ -1742,7 +1789,7 @@ class LossEvaluator:
     same).  `reduce`: a callable summing it over the ranks that hold the other views (gslm.parallel.allreduce_loss)."""
 
     def __init__(self, model, cams, bg, device="cuda", batch=8, gts=None, alpha_masks=None, reduce=None, streams=3,
-                 device_count=False, train_exposure=False, fused_exposure=False):
+                 device_count=False, train_exposure=False, fused_exposure=False, robust=None):
         """train_exposure: the loss is taken on the exposed colour of each camera's row of model._exposure, as
         LMProblem(train_exposure=True) takes it: 2 sum ||m clamp01(C) - gt||^2.  evaluate() then renders each view
         with the full forward and runs gslm_lm_residual_exposure in its loss-only mode (no fused loss epilogue, no
@@ -1750,7 +1797,16 @@ class LossEvaluator:
         fused_exposure (with train_exposure, without device_count -- else ValueError): the exposure is applied in the
         blend's loss epilogue instead (gslm_rasterize_loss_exposure: the same per-pixel residuals, summed per tile).
         evaluate() then takes its ordinary path -- batches, side streams, cached depth orders -- and evaluate_points
-        is allowed: every set carries its own _exposure, and view i at set a uses row exp_idx[i] of it."""
+        is allowed: every set carries its own _exposure, and view i at set a uses row exp_idx[i] of it.
+        robust: None, ("huber", delta) or ("cauchy", delta), as LMProblem takes it: the loss is 2 sum rho(r^2), summed
+        in the blends' epilogues (gslm_rasterize_loss_robust and its slot and sets forms) -- batches, side streams
+        and GSLM_LOSS_SET_GROUP as ever.  ValueError with device_count=True or train_exposure (neither blend has a
+        robust form)."""
+        self.robust = robust_option(robust)
+        if self.robust is not None and (device_count or train_exposure):
+            raise ValueError("robust: the device-count blend and the exposure blends have no robust form "
+                             "(device_count=False, train_exposure=False)")
+        self._robust = _robust_struct(self.robust)
         self.model = model
         self.train_exposure = bool(train_exposure)
         self.fused_exposure = bool(fused_exposure)
@@ -1856,9 +1912,15 @@ class LossEvaluator:
 
     def _blend_loss(self, vw, P, sl, N, i, xrows, scr, out, sh):
         """gslm_rasterize_loss of view i from slot sl into the double at `out`; xrows (fused_exposure): the data
-        pointer of the exposure rows, the blend then gslm_rasterize_loss_exposure with the camera's row."""
+        pointer of the exposure rows, the blend then gslm_rasterize_loss_exposure with the camera's row; with `robust`
+        gslm_rasterize_loss_robust."""
         mp = self._mask_ptr(i)
-        if xrows is None:
+        if self._robust is not None:
+            check(lib.gslm_rasterize_loss_robust(ctypes.byref(vw), P, sl["geom"].data_ptr(), sl["binning"].data_ptr(),
+                                                 sl["binning"].numel(), N, self.gts[i].data_ptr(), mp,
+                                                 ctypes.byref(self._robust), scr.data_ptr(), scr.numel() * 8, out, 0,
+                                                 sh), "gslm_rasterize_loss_robust")
+        elif xrows is None:
             check(lib.gslm_rasterize_loss(ctypes.byref(vw), P, sl["geom"].data_ptr(), sl["binning"].data_ptr(),
                                           sl["binning"].numel(), N, self.gts[i].data_ptr(), mp, scr.data_ptr(),
                                           scr.numel() * 8, out, 0, sh), "gslm_rasterize_loss")
@@ -2119,6 +2181,12 @@ class LossEvaluator:
                                 self.gts[i].data_ptr(), mp, xp, scr.data_ptr(), scr.numel() * 8, lp, 0, sh),
                                 "gslm_rasterize_loss_sets_exposure")
                             continue
+                        if self._robust is not None:
+                            check(lib.gslm_rasterize_loss_sets_robust(
+                                ctypes.byref(vw), P, gg, na, a0, sb, binning.data_ptr(), binning.numel(), N,
+                                self.gts[i].data_ptr(), mp, ctypes.byref(self._robust), scr.data_ptr(),
+                                scr.numel() * 8, lp, 0, sh), "gslm_rasterize_loss_sets_robust")
+                            continue
                         check(lib.gslm_rasterize_loss_sets(ctypes.byref(vw), P, gg, na, a0, sb, binning.data_ptr(),
                                                            binning.numel(), N, self.gts[i].data_ptr(), mp,
                                                            scr.data_ptr(), scr.numel() * 8, lp, 0, sh),
@@ -2131,6 +2199,12 @@ class LossEvaluator:
                             ctypes.byref(vw), P, sl["geoms"][a].data_ptr(), sb, binning.data_ptr(), binning.numel(), N,
                             a, n, self.gts[i].data_ptr(), mp, xs[a] + xoff, scr.data_ptr(), scr.numel() * 8,
                             losses[a].data_ptr() + 8 * i, 0, sh), "gslm_rasterize_loss_slot_exposure")
+                        continue
+                    if self._robust is not None:
+                        check(lib.gslm_rasterize_loss_slot_robust(
+                            ctypes.byref(vw), P, sl["geoms"][a].data_ptr(), sb, binning.data_ptr(), binning.numel(), N,
+                            a, n, self.gts[i].data_ptr(), mp, ctypes.byref(self._robust), scr.data_ptr(),
+                            scr.numel() * 8, losses[a].data_ptr() + 8 * i, 0, sh), "gslm_rasterize_loss_slot_robust")
                         continue
                     check(lib.gslm_rasterize_loss_slot(ctypes.byref(vw), P, sl["geoms"][a].data_ptr(), sb,
                                                        binning.data_ptr(), binning.numel(), N, a, n, self.gts[i].data_ptr(),
@@ -2193,7 +2267,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
             verbose=False, device="cuda", sh_projection="auto", recursion="fused", exchange="auto", group=None,
             val_batch=8, timing=False, backend=None, line_search="union", val_at_start=False, cache_val=True,
             multiview="loop", union_active=False, train_exposure=False, val_exposure="forward", precond=None,
-            damping="fixed", marquardt_floor=0.0):
+            damping="fixed", marquardt_floor=0.0, robust=None):
     """One LM step of train_jvp.py:237-289: loss, CGLS on the normal equations, backtracking line search.
 
     Single process: LMProblem over `cams` (with one training view the SH-rest group of the CG vectors is carried
@@ -2239,6 +2313,11 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     given).  The single-process step with multiview="loop", recursion="fused", mask_xyz=True, no trained exposure and
     no backend, with either precond -- anything else, another string, or a marquardt_floor without it raises
     ValueError.  The result reports `damping`.
+    robust: None (today's step, launch for launch), ("huber", delta) or ("cauchy", delta): the step minimises
+    2 sum rho(r^2) by iteratively reweighted least squares (LMProblem(robust=...)) and the line search takes the same
+    robust loss on the validation views (LossEvaluator(robust=...)).  With either multiview, union_active, either
+    precond, either damping and either line_search; ValueError for anything else than the three forms, and for a
+    sharded run, a backend, recursion="cgls", train_exposure=True or mask_xyz=False.  The result reports `robust`.
     backend: (problem_cls, evaluator_cls, solver) replacing (LMProblem, LossEvaluator, cgls_fused) -- the CPU
     multi-process tests run this same driver, sharding and reductions on the oracle restatement."""
     import time
@@ -2282,6 +2361,12 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
             raise ValueError("damping='marquardt': damp is the per-group multiplier lambda and must be given")
     elif marquardt_floor != 0.0:
         raise ValueError("marquardt_floor is an option of damping='marquardt'")
+    robust = robust_option(robust)
+    if robust is not None and (sharded or backend is not None or recursion != "fused" or train_exposure or
+                               not mask_xyz):
+        raise ValueError("robust is the single-process step with recursion='fused', mask_xyz=True, no trained "
+                         "exposure and no backend")
+    rob_kw = {"robust": robust} if robust is not None else {}
     exp_kw = {"train_exposure": True} if train_exposure else {}
     damp_kw = {"damping": "marquardt", "marquardt_floor": marquardt_floor} if damping == "marquardt" else {}
     fused_exposure = val_exposure == "fused"
@@ -2305,7 +2390,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     else:
         kw = {"union_active": True} if (union_active and problem_cls is BatchedLMProblem) else {}
         prob = problem_cls(model, cams, bg, mask_xyz=mask_xyz, damp=damp, device=device, sh_projection=sh_projection,
-                           **kw, **exp_kw, **damp_kw)
+                           **kw, **exp_kw, **damp_kw, **rob_kw)
     start_loss = prob.evaluate()
     if recursion == "cgls":
         lap("evaluate_rhs_ms")
@@ -2333,7 +2418,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     # next while the model, the validation cameras (held by it, so their ids stay theirs) and the settings are the same
     imgs = [(getattr(c, "original_image", None), getattr(c, "alpha_mask", None)) for c in mine_val]
     vkey = (id(model), model.active_sh_degree, tuple(id(c) for c in mine_val), tuple(id(t) for p in imgs for t in p),
-            str(device), val_batch, evaluator_cls, sharded, id(group), bool(train_exposure), val_exposure,
+            str(device), val_batch, evaluator_cls, sharded, id(group), bool(train_exposure), val_exposure, robust,
             tuple(float(x) for x in torch.as_tensor(bg).reshape(-1).tolist()))
     hit = _VAL_CACHE.get("last") if cache_val else None
     if hit is not None and hit[0] == vkey:
@@ -2343,7 +2428,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     else:
         _VAL_CACHE.pop("last", None)
         val = evaluator_cls(model, mine_val, bg, device=device, batch=val_batch,
-                            reduce=(lambda x: allreduce_loss(x, group)) if sharded else None, **exp_kw,
+                            reduce=(lambda x: allreduce_loss(x, group)) if sharded else None, **exp_kw, **rob_kw,
                             **({"fused_exposure": True} if fused_exposure else {}),
                             # (GSLM_VAL_STREAMS: the side-stream count, an A/B override of LossEvaluator's default)
                             **({"streams": int(os.environ["GSLM_VAL_STREAMS"])} if "GSLM_VAL_STREAMS" in os.environ else {}))
@@ -2395,6 +2480,8 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
         out["precond"] = precond
     if damping != "fixed":
         out["damping"] = damping
+    if robust is not None:
+        out["robust"] = robust
     if val_at_start:
         out["val_start_loss"] = val_start
     if union and getattr(val, "union_counts", None):

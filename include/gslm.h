@@ -234,6 +234,32 @@ int gslm_rasterize_loss_sets_exposure(const gslm_view* view, int64_t P, const vo
                                       int64_t num_rendered, const float* gt, const float* alpha_mask,
                                       const float* const* exposure, void* scratch, size_t scratch_bytes,
                                       double* const* loss_dev, int32_t accumulate, void* stream);
+/* The three loss blends under a robust loss (still ABI 9, additive; rho and its arithmetic: at
+ * gslm_lm_residual_robust below):
+ * the plain form's arguments, checks, scratch sizes, visits and per-pixel residuals r, with the per-tile sum taking
+ * rho(r^2) -- gslm_lm_residual_robust's double expression on the same float r and the same float test -- in place
+ * of r^2.  `robust` is read on the host and passed by value; one block serves all sets of a call.  robust NULL or kind
+ * GSLM_ROBUST_NONE launches the plain form's kernel (the same bits); an unknown kind, or a delta that is not finite
+ * and > 0, returns GSLM_ERR_INVALID before any launch.  There is no device-count form and no exposure x robust form. */
+enum { GSLM_ROBUST_NONE = 0, GSLM_ROBUST_HUBER = 1, GSLM_ROBUST_CAUCHY = 2 };
+typedef struct {
+  int32_t kind;  /* GSLM_ROBUST_* */
+  float delta;   /* the scale: finite and > 0 (ignored with GSLM_ROBUST_NONE) */
+} gslm_robust;
+int gslm_rasterize_loss_robust(const gslm_view* view, int64_t P, void* geom, void* binning, size_t binning_bytes,
+                               int64_t num_rendered, const float* gt, const float* alpha_mask,
+                               const gslm_robust* robust, void* scratch, size_t scratch_bytes,
+                               double* loss_dev, int32_t accumulate, void* stream);
+int gslm_rasterize_loss_slot_robust(const gslm_view* view, int64_t P, const void* geom, size_t set_bytes,
+                                    const void* binning, size_t binning_bytes, int64_t num_rendered, int32_t slot,
+                                    int32_t n_sets, const float* gt, const float* alpha_mask,
+                                    const gslm_robust* robust, void* scratch, size_t scratch_bytes,
+                                    double* loss_dev, int32_t accumulate, void* stream);
+int gslm_rasterize_loss_sets_robust(const gslm_view* view, int64_t P, const void* const* geoms, int32_t n,
+                                    int32_t first_set, size_t set_bytes, const void* binning, size_t binning_bytes,
+                                    int64_t num_rendered, const float* gt, const float* alpha_mask,
+                                    const gslm_robust* robust, void* scratch, size_t scratch_bytes,
+                                    double* const* loss_dev, int32_t accumulate, void* stream);
 /* Convenience: gslm_preprocess + gslm_num_rendered + gslm_rasterize.  If binning_bytes is too
  * small returns GSLM_ERR_CAPACITY with *out_num_rendered set (geometry is valid: call
  * gslm_rasterize with a larger buffer). */
@@ -793,6 +819,28 @@ size_t gslm_residual_scratch_bytes(int32_t H, int32_t W);
 int gslm_lm_residual(int32_t H, int32_t W, const float* color, const float* gt, const float* alpha_mask,
                      float* residual, float* weight, float* seed, void* scratch, size_t scratch_bytes,
                      double* loss_dev, int32_t accumulate, void* stream);
+
+/* ---- Robust losses of the LM step (still ABI 9, additive): iteratively reweighted least squares in the first-order
+ * Triggs form.  The loss is 2 sum rho(r^2) over the residual elements r of gslm_lm_residual, and with
+ * rho' = rho'(r^2) taken at the linearisation point the weight and the seed are gslm_lm_residual's times rho' -- so
+ * J^T b is exactly -1/2 grad loss and every product downstream is 2 J^T (W rho') J + D without knowing about it.
+ *   HUBER   rho(s) = s                          rho' = 1                 where |r| <= delta
+ *                    2 delta |r| - delta^2            delta / |r|        elsewhere
+ *   CAUCHY  rho(s) = delta^2 log1p(s / delta^2) rho' = 1 / (1 + t t),    t = r / delta
+ * Arithmetic: one float test per element, fabsf(r) <= delta, serves rho and rho'; rho' in float with correctly rounded
+ * divisions and uncontracted products; rho in double from (double)r and (double)delta.  A NaN r gives a NaN weight,
+ * seed and loss.  gslm_robust {kind, delta}: declared with the loss blends above. */
+/* gslm_lm_residual under a robust loss: the same arguments, optional outputs, scratch size and two-pass double
+ * reduction, with
+ *   residual = r                                        (unscaled: the residual the caller inspects)
+ *   weight   = ((m m) 1[0 <= color <= 1]) rho'
+ *   seed     = (((-2 m) 1[0 <= color <= 1]) r) rho'
+ *   *loss_dev = [*loss_dev if accumulate] + 2 sum rho.
+ * robust NULL or kind GSLM_ROBUST_NONE is gslm_lm_residual itself (the same kernel: the same bits).  An unknown kind,
+ * or a delta that is not finite and > 0, returns GSLM_ERR_INVALID before any launch, the outputs untouched. */
+int gslm_lm_residual_robust(int32_t H, int32_t W, const float* color, const float* gt, const float* alpha_mask,
+                            const gslm_robust* robust, float* residual, float* weight, float* seed, void* scratch,
+                            size_t scratch_bytes, double* loss_dev, int32_t accumulate, void* stream);
 
 /* ---- SSIM residual of the LM step (solver/batch_training_loss.py:18-30 with
  * disable_ssim=False, FUSED_SSIM_AVAILABLE=False, on utils/loss_utils.py:91-122 ssim_per_pixel) ----
