@@ -59,6 +59,26 @@ def _f32(t):
     return t.contiguous()
 
 
+def _check_inputs(**tensors):
+    """Refuses, before anything reaches the library, a tensor argument that is not float32 (TypeError) or not on the
+    CUDA device of means3D (ValueError, means3D itself included): the kernels read raw pointers, and a host pointer
+    or another card's pointer would fault there.  Every dtype is looked at first, so the dtype refusal does not
+    depend on where the tensors live."""
+    # an empty tensor is an absent argument, as in _f32 (upstream's callers pass torch.Tensor([]) for those); means3D
+    # is looked at either way
+    given = {k: t for k, t in tensors.items() if t is not None and (t.numel() or k == "means3D")}
+    for name, t in given.items():
+        if t.dtype != torch.float32:
+            raise TypeError(f"rasterizer inputs must be float32, got {t.dtype} for {name}")
+    device = given["means3D"].device
+    if device.type != "cuda":
+        raise ValueError(f"rasterizer inputs must be on a CUDA device, got means3D on {device}")
+    for name, t in given.items():
+        if t.device != device:
+            raise ValueError(f"rasterizer inputs must be on the device of means3D ({device}), got {name} on "
+                             f"{t.device}")
+
+
 def _gaussians(P, means3D, opacities, scales, rotations, cov3D, sh, dc, colors):
     """gslm_gaussians for activated inputs; sh [P,K,3] (or rest [P,K-1,3] with dc [P,1,3])."""
     if dc is not None:
@@ -128,6 +148,8 @@ class _RasterizeGaussians(torch.autograd.Function):
     @staticmethod
     def forward(means3D, means2D, sh, dc, colors_precomp, opacities, scales, rotations, cov3Ds_precomp,
                 raster_settings):
+        _check_inputs(means3D=means3D, means2D=means2D, shs=sh, dc=dc, colors_precomp=colors_precomp,
+                      opacities=opacities, scales=scales, rotations=rotations, cov3D_precomp=cov3Ds_precomp)
         device = means3D.device
         P = means3D.shape[0]
         view = _lib.view_from_settings(raster_settings)
@@ -171,19 +193,22 @@ class _RasterizeGaussians(torch.autograd.Function):
         # call's, element for element (compared on the device), returns that call's gradients -- bitwise what the
         # kernels would produce again.  They stay referenced here until the graph is freed, so autograd clones them
         # before accumulating and never writes into them.  GSLM_BWD_MEMO=0 turns it off.
+        # The saved tensors are read first, on a memo hit too: reading them is what runs autograd's version check, so
+        # an input written in place since the forward raises here instead of being answered with gradients of the
+        # values it had.
+        saved = ctx.saved_tensors
         memo = getattr(ctx, "bw_memo", None)
         if memo is not None and _same_cotangent(memo[0], grad_color) and _same_cotangent(memo[1], grad_invdepth):
             return memo[2]
-        out = _RasterizeGaussians._backward(ctx, grad_color, grad_invdepth)
+        out = _RasterizeGaussians._backward(ctx, saved, grad_color, grad_invdepth)
         if _BWD_MEMO:
             ctx.bw_memo = (None if grad_color is None else grad_color.detach().clone(),
                            None if grad_invdepth is None else grad_invdepth.detach().clone(), out)
         return out
 
     @staticmethod
-    def _backward(ctx, grad_color, grad_invdepth):
-        (means3D, sh, dc, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, geom, binning,
-         image) = ctx.saved_tensors
+    def _backward(ctx, saved, grad_color, grad_invdepth):
+        means3D, sh, dc, colors_precomp, opacities, scales, rotations, cov3Ds_precomp, geom, binning, image = saved
         st = ctx.raster_settings
         device = means3D.device
         P = means3D.shape[0]
@@ -198,8 +223,10 @@ class _RasterizeGaussians(torch.autograd.Function):
         # 1M Gaussians SH 3)
         z = lambda t: None if t is None else torch.empty_like(t)
         d_means2D = torch.empty(P, 3, dtype=torch.float32, device=device)
-        d_means3D = torch.empty_like(means3D)
-        d_opac = torch.empty_like(opacities)
+        # the kernel writes these row-major through data_ptr(): made from the shape, never with the caller's strides
+        # (empty_like of a column-major means3D would be column-major, and autograd checks shapes only)
+        d_means3D = torch.empty(means3D.shape, dtype=torch.float32, device=device)
+        d_opac = torch.empty(opacities.shape, dtype=torch.float32, device=device)
         d_scales, d_rot, d_cov = z(s), z(r), z(c3)
         d_sh, d_dc, d_col = z(shc), z(dcc), z(col)
         grads = _lib.make_grads(means2D=d_means2D, means3D=d_means3D, opacities=d_opac, scales=d_scales,
