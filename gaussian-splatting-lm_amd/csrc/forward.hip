@@ -608,16 +608,12 @@ __global__ __launch_bounds__(256) void k_quad_live(ViewK v, const uint2* __restr
                                                     const uint32_t* __restrict__ n_contrib, uint32_t* point_list) {
   __shared__ float4 s_a[4][64];  // [wave][lane]: x, y, conic a, conic b
   __shared__ float2 s_b[4][64];  //               conic c, opacity
-  const int tile = (int)tile_order[blockIdx.x];
-  const int tile_x = tile % v.gx, tile_y = tile / v.gx;
+  const TilePix p = tile_pix(v, tile_order);
   const int tid = threadIdx.x, q = tid >> 6, lane = tid & 63;
-  int px, py;
-  tile_pixel(tile_x, tile_y, tid, px, py);
-  const bool inside = px < v.W && py < v.H;
-  const uint32_t my_last = inside ? n_contrib[(int64_t)py * v.W + px] : 0u;
-  const uint2 range = ranges[tile];
-  const int wm = __builtin_amdgcn_readfirstlane((int)min(neff[4 * tile + q], range.y - range.x));
-  const float pxf = (float)px, pyf = (float)py;
+  const uint32_t my_last = p.inside ? n_contrib[p.pid] : 0u;
+  const uint2 range = ranges[p.tile];
+  const int wm = __builtin_amdgcn_readfirstlane((int)min(neff[4 * p.tile + q], range.y - range.x));
+  const float pxf = (float)p.px, pyf = (float)p.py;
   uint32_t* pl = point_list + range.x;
   float4* sa = s_a[q];
   float2* sb = s_b[q];

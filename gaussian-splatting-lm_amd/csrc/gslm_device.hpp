@@ -51,9 +51,6 @@ struct ViewK {
   const double* stop = nullptr;
 };
 
-// torch.clamp(x, 0, 1) (the reference's rendered_image.clamp(0, 1), batch_render.py:118): a NaN stays a NaN, as in
-// torch -- fminf / fmaxf would turn it into 0 or 1 and hide it from the reference's NaN asserts (solver_functions.py:
-// 125-130).  Identical to fminf(fmaxf(x, 0), 1) for every other input.
 // Thread-strided in-order sum ((x[t] + x[t + T]) + x[t + 2T]) + ... (T = blockDim.x) with the loads issued 8 at a
 // time: one memory latency per 8 partials, where the one-at-a-time loop waited on every load.  The additions keep
 // that loop's order (a skipped slot adds nothing), so the sum is bitwise the same -- the deterministic reductions'
@@ -77,6 +74,26 @@ __device__ __forceinline__ F strided_sum_in_order(const F* __restrict__ x, int64
   return strided_sum_in_order(x, n, (int64_t)blockDim.x);
 }
 
+// The deterministic sum of one double per thread over a 256-thread block, in two steps.  wave_sum_store: the 64-lane
+// __shfl_down tree (offsets 32 .. 1, all lanes active), lane 0's total into s4[wave].  sum4, after a block barrier:
+// the four waves' totals as ((s0 + s1) + s2) + s3.  The tree and that grouping are the contract: every loss and every
+// exposure row sum is compared bitwise from build to build.  A kernel with several sums stores them all before its one
+// barrier; block_sum4 is the single-sum form, barrier included (s4: 4 doubles of LDS the caller owns).
+__device__ __forceinline__ void wave_sum_store(double acc, double* s4) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
+  if ((threadIdx.x & 63) == 0) s4[threadIdx.x >> 6] = acc;
+}
+__device__ __forceinline__ double sum4(const double* s4) { return ((s4[0] + s4[1]) + s4[2]) + s4[3]; }
+__device__ __forceinline__ double block_sum4(double acc, double* s4) {
+  wave_sum_store(acc, s4);
+  __syncthreads();
+  return sum4(s4);
+}
+
+// torch.clamp(x, 0, 1) (the reference's rendered_image.clamp(0, 1), batch_render.py:118): a NaN stays a NaN, as in
+// torch -- fminf / fmaxf would turn it into 0 or 1 and hide it from the reference's NaN asserts (solver_functions.py:
+// 125-130).  Identical to fminf(fmaxf(x, 0), 1) for every other input.
 __device__ __forceinline__ float clamp01(float x) { return x < 0.0f ? 0.0f : (x > 1.0f ? 1.0f : x); }
 
 // block-uniform early exit of a product kernel once the device-side CG stopping tests fired

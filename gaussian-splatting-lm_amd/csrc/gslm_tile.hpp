@@ -7,6 +7,12 @@
 //   primal_test       a visit's alpha and its skip decisions, rounded exactly as the forward's
 //   combine_waves     one value slot's four per-wave partials, in fixed quadrant order
 // Each pass keeps its own loop nest (rounds, hit words, visits) and calls these in place.
+// The front-to-back wave passes (render_fwd.hip: k_render_fwd_wave, k_render_loss_sets) share, in the same way:
+//   FwdPix            a lane's blend state, with the stopped-lane encoding of T, and its composite over the background
+//   stage_hit         one list entry's record into the wave's three lane-indexed LDS slots
+//   load_hit          entry j of those slots, the loads pinned together
+//   fwd_visit         one blend visit: the roundings that decide which Gaussians every other pass visits
+//   loss_term         one channel's term of a pixel's loss (plain, exposure, robust)
 //
 // VJP accumulation strategy (MI355X-specific): instead of upstream's per-pixel global atomicAdd
 // (10 atomics per pixel-Gaussian pair), every wave reduces a Gaussian's per-pixel contributions
@@ -215,6 +221,96 @@ __device__ __forceinline__ float combine_waves(const float* s_acc, int sq, int i
   const float p2 = (mask & 4u) ? a2 : 0.f;
   const float p3 = (mask & 8u) ? a3 : 0.f;
   return ((p0 + p1) + p2) + p3;
+}
+
+// ---- the front-to-back wave passes' parts (render_fwd.hip) ----
+// One independent wave per 8x8 quadrant walks the tile's list 64 positions per round: each lane fetches one entry, the
+// hits stage their record in the wave's own LDS slots (stage_hit), and the wave visits the round's hit bits in list
+// order (load_hit, fwd_visit) until live_update leaves no lane.  The loop nests stay in the kernels.
+
+// A lane's blend state.  A stopped lane (or one outside the image) carries T <= 0: minus its transmittance at the stop,
+// which a live lane (T >= 1e-4) never is.  Every visit then runs the same per-lane arithmetic with no boolean lane
+// state across iterations (each one would cost a few scalar mask instructions per visit; with them the loop was bound
+// by its scalar instructions, not VALU): a stopped lane's test_T = T (1 - u) <= 0 stops it again, with weight 0, and
+// -|T| keeps T -- one select with source modifiers, where a separate stop-transmittance register cost two VALU.
+struct FwdPix {
+  float T, C0, C1, C2;
+  // the transmittance the reference keeps: at the stop, else after the last Gaussian
+  __device__ __forceinline__ float final_T() const { return T > 0.0f ? T : -T; }
+  // the colour over the background bg, Tf = final_T()
+  __device__ __forceinline__ void composite(float Tf, const float* bg, float R[3]) const {
+    R[0] = C0 + Tf * bg[0];
+    R[1] = C1 + Tf * bg[1];
+    R[2] = C2 + Tf * bg[2];
+  }
+};
+__device__ __forceinline__ FwdPix fwd_pix(bool inside) { return {inside ? 1.0f : 0.0f, 0.f, 0.f, 0.f}; }
+
+// A list entry's render record as the wave passes stage it: [x y conic a b | conic c, opacity, r, g | b, 1/depth, ..]
+struct HitRec {
+  float4 a, b, c;
+};
+__device__ __forceinline__ HitRec load_rec(const float4* __restrict__ rec, uint32_t g) {
+  const float4* r = rec + RECS * (size_t)g;
+  return {r[0], r[1], r[2]};
+}
+// the lane's record into the wave's slots lane, 64 + lane, 128 + lane (s: 3 x 64 float4, the wave's own)
+__device__ __forceinline__ void stage_hit(float4* s, int lane, const HitRec& r) {
+  s[lane] = r.a;
+  s[64 + lane] = r.b;
+  s[128 + lane] = r.c;
+}
+// Entry j of the slots, the whole record in one LDS round trip at the top of the visit: the empty asm pins the colour
+// loads there (otherwise they are fetched after the alpha test, a second exposed LDS latency).  INV: the visit reads
+// the inverse depth too.
+template <bool INV>
+__device__ __forceinline__ HitRec load_hit(const float4* s, int j) {
+  const HitRec h = {s[j], s[64 + j], s[128 + j]};
+  if constexpr (INV) asm volatile("" : : "v"(h.b.z), "v"(h.b.w), "v"(h.c.x), "v"(h.c.y));
+  else asm volatile("" : : "v"(h.b.z), "v"(h.b.w), "v"(h.c.x));
+  return h;
+}
+
+// One blend visit of the lane at pixel centre (pxf, pyf): upstream renderCUDA's roundings, which decide the stop and
+// the skips and so which Gaussians every other pass visits (primal_test rounds power and alpha the same way).
+// Returns whether the lane stops here (or had stopped); wt is the weight its colour entered the sums with, > 0 exactly
+// where the reference blends the Gaussian.
+__device__ __forceinline__ bool fwd_visit(const HitRec& h, float pxf, float pyf, FwdPix& p, float& wt) {
+  const float dx = h.a.x - pxf, dy = h.a.y - pyf;
+  const float power = gpower(h.a.z, h.a.w, h.b.x, dx, dy);
+  const float alpha = fminf(0.99f, h.b.y * gexp(power));
+  // u: the alpha the reference blends, 0 where it skips the Gaussian (power > 0, alpha < 1/255): T * (1 - 0)
+  // and colour * 0 leave T and the sums unchanged bitwise (the sums start at +0, colours and 1/depth are >= 0)
+  float u = alpha >= 1.0f / 255.0f ? alpha : 0.0f;
+  u = power > 0.0f ? 0.0f : u;
+  const float test_T = p.T * (1.0f - u);
+  // a live lane has T >= 1e-4, so with u = 0 it never stops here; a stopped lane (T <= 0) re-stops harmlessly
+  const bool stop = test_T < 0.0001f;
+  wt = stop ? 0.0f : u * p.T;
+  // the colour sums decide nothing (the stop and skip tests above are upstream's roundings): one FMA each
+  p.C0 = __builtin_fmaf(h.b.z, wt, p.C0);
+  p.C1 = __builtin_fmaf(h.b.w, wt, p.C1);
+  p.C2 = __builtin_fmaf(h.c.x, wt, p.C2);
+  p.T = stop ? -fabsf(p.T) : test_T;
+  return stop;
+}
+
+// Channel c's term of a pixel's loss, in double: r = m clamp01(C_c) - gt_c (gslm_lm_residual's arithmetic), then r^2.
+// The caller sums c = 0, 1, 2 onto a 0 in that order, for pixels inside the image only (with an offset column the
+// exposed colour of a lane outside would not be 0).  R: the composited colour; gt: the ground truth's channel c.
+// EXPO: C_c = ((R0 x[c] + R1 x[4 + c]) + R2 x[8 + c]) + x[4 c + 3], the camera's 3x4 exposure map x
+// (k_lm_residual_exposure's arithmetic in its order); x is not read otherwise.
+// ROBUST (never with EXPO): robust_rho(rb, r), k_lm_residual<true>'s expression on the same float r, for r^2.
+// One channel and not the pixel's sum: with the three-term sum in here, k_render_loss_sets<1, false, true> flattens
+// robust_rho's branches into selects and takes 58 VGPRs for 41.
+template <bool EXPO, bool ROBUST>
+__device__ __forceinline__ double loss_term(const float R[3], const float x[12], int c, float m, float gt,
+                                            const gslm_robust rb) {
+  static_assert(!ROBUST || !EXPO, "the robust loss belongs to the plain loss epilogue");
+  const float Cc = EXPO ? ((R[0] * x[c] + R[1] * x[4 + c]) + R[2] * x[8 + c]) + x[4 * c + 3] : R[c];
+  const float r = m * clamp01(Cc) - gt;
+  if constexpr (ROBUST) return robust_rho(rb, r);
+  else return (double)r * (double)r;
 }
 
 // Screen-space gradient of one (tile, Gaussian) pair, value index q:

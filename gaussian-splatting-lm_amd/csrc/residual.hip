@@ -56,25 +56,16 @@ __global__ __launch_bounds__(RES_THREADS) void k_lm_residual(int64_t HW, const f
       }
     }
   }
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-  if (lane == 0) s[w] = acc;
-  __syncthreads();
-  if (tid == 0) part[blockIdx.x] = ((s[0] + s[1]) + s[2]) + s[3];
+  const double sum = block_sum4(acc, s);
+  if (threadIdx.x == 0) part[blockIdx.x] = sum;
 }
 
 __global__ __launch_bounds__(RES_THREADS) void k_lm_loss_final(const double* __restrict__ part, int np, int accumulate,
                                                                double* __restrict__ loss) {
   __shared__ double s[RES_THREADS / 64];
-  double acc = strided_sum_in_order(part, np);
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-  if (lane == 0) s[w] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    const double l = 2.0 * (((s[0] + s[1]) + s[2]) + s[3]);  // [r; r] aliasing
+  const double sum = block_sum4(strided_sum_in_order(part, np), s);
+  if (threadIdx.x == 0) {
+    const double l = 2.0 * sum;  // [r; r] aliasing
     *loss = accumulate ? *loss + l : l;
   }
 }
@@ -106,6 +97,7 @@ __device__ __forceinline__ void exposure_rows_add(double* rows, float R0, float 
 template <int N>
 __device__ __forceinline__ void block_sums_store(double* acc, double* s, double* __restrict__ part) {
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  // wave_sum_store's tree, written out: called here it costs k_lm_residual_exposure four VGPRs (80 for 76)
 #pragma unroll
   for (int k = 0; k < N; ++k) {
     double a = acc[k];
@@ -114,7 +106,7 @@ __device__ __forceinline__ void block_sums_store(double* acc, double* s, double*
     if (lane == 0) s[4 * k + w] = a;
   }
   __syncthreads();
-  if (tid < N) part[tid * EXP_PART + blockIdx.x] = ((s[4 * tid] + s[4 * tid + 1]) + s[4 * tid + 2]) + s[4 * tid + 3];
+  if (tid < N) part[tid * EXP_PART + blockIdx.x] = sum4(s + 4 * tid);
 }
 
 __global__ __launch_bounds__(RES_THREADS) void k_lm_residual_exposure(
@@ -175,14 +167,9 @@ __global__ __launch_bounds__(RES_THREADS) void k_exposure_rows_final(const doubl
                                                                      float* __restrict__ out) {
   __shared__ double s[RES_THREADS / 64];
   if (stop != nullptr && *stop != 0.0) return;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, k = blockIdx.x;
-  double acc = strided_sum_in_order(part + (size_t)k * EXP_PART, np);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o, 64);
-  if (lane == 0) s[w] = acc;
-  __syncthreads();
-  if (tid == 0) {
-    const float sum = (float)(((s[0] + s[1]) + s[2]) + s[3]);
+  const int k = blockIdx.x;
+  const float sum = (float)block_sum4(strided_sum_in_order(part + (size_t)k * EXP_PART, np), s);
+  if (threadIdx.x == 0) {
     float base = overwrite ? 0.0f : out[k];
     if (v) base += damp * v[k];
     out[k] = base + sum;
