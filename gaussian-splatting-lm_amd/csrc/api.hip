@@ -860,40 +860,157 @@ static int build_xpby(const gslm_matvec_opts* opts, const gslm_grads* vin, int R
 
 static const uint32_t* active_params_bind(const void* block, int64_t na, GaussK* g);
 
-// gslm_matvec_view_ex (na < 0) and gslm_matvec_view_active (na >= 0: the groups of vin, y and the fused direction
-// update hold the na Gaussians ids[0 .. na) only)
-static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gslm_grads* vin,
-                       const float* pixel_weight, int32_t mask_xyz, const void* geom, const void* binning,
-                       int64_t N, const void* image, void* scratch, size_t scratch_bytes, const gslm_grads* y,
-                       const gslm_matvec_opts* opts, const int32_t* ids, int64_t na, const uint32_t* hrow,
-                       void* stream) {
-  DebugScope dbg_scope(view != nullptr && view->debug != 0, stream);
-  Bound b;
-  int st = bind_all(view, gi, geom, binning, N, image, scratch, scratch_bytes, &b);
-  if (st) return st;
-  if (!vin || !y || !pixel_weight) { set_error("matvec: NULL argument"); return GSLM_ERR_INVALID; }
-  // (one extension struct lies behind the base: refused before either flag's extension is read)
-  if (opts && (opts->flags & GSLM_MV_DAMP_VEC) && (opts->flags & (GSLM_MV_LEAN | GSLM_MV_EXPOSURE))) {
-    set_error("matvec: GSLM_MV_DAMP_VEC excludes GSLM_MV_LEAN and GSLM_MV_EXPOSURE");
+// ---- the decoded product call: every refusal of the product entry points happens while a Plan is built, before the
+// first launch; running a Plan can fail on a HIP error only ----
+// A call as bits: the entry point (E_*), and what its options and arguments ask for (F_*).
+enum : uint32_t {
+  E_MATVEC_EX = 1u << 0, E_MATVEC_ACTIVE = 1u << 1, E_GATHER_SCREEN = 1u << 2, E_GATHER_VIEWS = 1u << 3,
+  E_TANGENT_VIEWS = 1u << 4, E_MATVEC = E_MATVEC_EX | E_MATVEC_ACTIVE, E_GATHER = E_GATHER_SCREEN | E_GATHER_VIEWS,
+  F_LEAN = 1u << 5, F_EXPOSURE = 1u << 6, F_DAMP_VEC = 1u << 7, F_PROJECTED = 1u << 8, F_SEED = 1u << 9,
+  F_JV_OUT = 1u << 10, F_TREC_IN = 1u << 11, F_REST_BASIS = 1u << 12, F_DAMP7 = 1u << 13, F_XPBY = 1u << 14,
+  F_TANGENT = 1u << 15, F_RENDER = 1u << 16, F_GATHER = 1u << 17, F_SCREEN = 1u << 18, F_OVERWRITE = 1u << 19,
+  F_UNMASKED = 1u << 20,    // mask_xyz = 0
+  F_TAIL_DIRTY = 1u << 21,  // no GSLM_MV_TAIL_CLEAN
+};
+// Which go together, once: a call in `mode` with any of `excludes` is refused (GSLM_ERR_INVALID).
+static const struct { uint32_t mode, excludes; const char* msg; } kExcludes[] = {
+    {E_GATHER, F_DAMP_VEC, "gather: GSLM_MV_DAMP_VEC is an option of gslm_matvec_view_ex / gslm_matvec_view_active"},
+    {E_MATVEC_EX, F_LEAN, "matvec: GSLM_MV_LEAN is an option of gslm_matvec_view_active"},
+    {E_MATVEC, F_REST_BASIS, "matvec: rest_basis is an option of gslm_tangent_views / gslm_gather_screen"},
+    {E_MATVEC_ACTIVE, F_UNMASKED | F_TAIL_DIRTY | F_SCREEN | F_TREC_IN,
+     "matvec_view_active: needs mask_xyz and GSLM_MV_TAIL_CLEAN (the list comes from that row map); no SCREEN stage, "
+     "no trec_in"},
+    {F_DAMP_VEC, F_DAMP7 | F_LEAN | F_EXPOSURE | F_UNMASKED | F_SEED | F_JV_OUT | F_SCREEN | F_TREC_IN | F_REST_BASIS,
+     "matvec: GSLM_MV_DAMP_VEC needs mask_xyz and excludes damp7, pixel_seed, jv_out, the SCREEN stage, trec_in, "
+     "rest_basis, GSLM_MV_LEAN and GSLM_MV_EXPOSURE"},
+    {F_EXPOSURE, F_LEAN | F_UNMASKED | F_SEED | F_JV_OUT | F_SCREEN | F_TREC_IN | F_REST_BASIS,
+     "matvec: GSLM_MV_EXPOSURE needs mask_xyz and excludes pixel_seed, jv_out, the SCREEN stage, trec_in, rest_basis "
+     "and GSLM_MV_LEAN"},
+    {F_PROJECTED, F_SCREEN, "matvec: GSLM_MV_SH_REST_PROJECTED is a single-view mode (no SCREEN stage)"},
+    {F_TREC_IN, F_TANGENT, "matvec: trec_in replaces the TANGENT stage"},
+    {F_SEED, F_UNMASKED | F_XPBY | F_TANGENT | F_SCREEN,
+     "matvec: pixel_seed (J^T seed) needs mask_xyz and excludes TANGENT / SCREEN / xpby"},
+    {F_JV_OUT, F_SEED | F_GATHER | F_SCREEN, "matvec: jv_out excludes pixel_seed, GATHER and SCREEN"},
+};
+static bool excluded(uint32_t f, uint32_t mode) {
+  for (const auto& r : kExcludes)
+    if (r.mode == mode && (f & mode) && (f & r.excludes)) {
+      set_error(r.msg);
+      return true;
+    }
+  return false;
+}
+
+struct Plan {
+  uint32_t f;                  // E_* | F_*
+  int64_t rows;                // rows of every group of vin and y
+  const double* stop;          // cg_ctl -> ViewK::stop
+  const double* damp7;
+  DampVecK dvec;               // F_DAMP_VEC
+  double *dot_out, *part;      // <v, y> and the gather's partials of it (dot_defer: the partials alone)
+  XpbyK xp;                    // F_XPBY, with the lean beta partials
+  GaussK t;                    // the tangent: vin's groups
+  GaussK gp;                   // the parameters the kernels read: g, or the list-order block (then with clamp_list)
+  const uint32_t* clamp_list;
+  const int32_t* ids;          // the active list (na < 0: none)
+  const uint32_t* hrow;
+  int64_t na;
+  const gslm_matvec_opts* o;   // trec_in, pixel_seed, jv_out and screen_out are read from the options as they are
+  const gslm_exposure_opts* expo;
+  RestK rc;
+  bool gather;                 // GATHER runs (no jv_out, no SCREEN); flat is built when it has rows
+  FlatK flat;
+};
+
+// The base options of `entry`; `accepts`: the F_* bits that entry point decodes (the others it has always ignored).
+static void plan_base(uint32_t entry, uint32_t accepts, const gslm_matvec_opts* o, bool mask_xyz, int M, Plan* pl) {
+  *pl = Plan{};
+  const int32_t st = (o && o->stages) ? o->stages : GSLM_STAGE_ALL, fl = o ? o->flags : 0;
+  uint32_t f = (st & GSLM_STAGE_TANGENT ? F_TANGENT : 0) | (st & GSLM_STAGE_RENDER ? F_RENDER : 0) |
+               (st & GSLM_STAGE_GATHER ? F_GATHER : 0) | (st & GSLM_STAGE_SCREEN ? F_SCREEN : 0) |
+               (st & GSLM_STAGE_OVERWRITE ? F_OVERWRITE : 0) | (fl & GSLM_MV_LEAN ? F_LEAN : 0) |
+               (fl & GSLM_MV_EXPOSURE ? F_EXPOSURE : 0) | (fl & GSLM_MV_DAMP_VEC ? F_DAMP_VEC : 0) |
+               ((fl & GSLM_MV_SH_REST_PROJECTED) && M > 1 ? F_PROJECTED : 0) | (fl & GSLM_MV_TAIL_CLEAN ? 0 : F_TAIL_DIRTY) |
+               (mask_xyz ? 0 : F_UNMASKED);
+  if (o) f |= (o->pixel_seed ? F_SEED : 0) | (o->jv_out ? F_JV_OUT : 0) | (o->trec_in ? F_TREC_IN : 0) |
+              (o->rest_basis ? F_REST_BASIS : 0) | (o->damp7 ? F_DAMP7 : 0) | (o->xpby_s ? F_XPBY : 0);
+  pl->f = entry | (f & (accepts | F_TANGENT | F_RENDER | F_GATHER | F_OVERWRITE | F_UNMASKED | F_TAIL_DIRTY));
+  pl->o = o;
+  pl->stop = o ? o->cg_ctl : nullptr;
+  pl->damp7 = (pl->f & F_DAMP7) ? o->damp7 : nullptr;
+  pl->na = -1;
+}
+
+// dot_vy and its scratch over `rows` rows (defer: GSLM_MV_LEAN's dot_defer, the partials without the finished dot)
+static int plan_dot(const char* who, int64_t rows, bool defer, Plan* pl) {
+  pl->dot_out = pl->o ? pl->o->dot_vy : nullptr;
+  if (!pl->dot_out && !defer) return GSLM_OK;
+  if (!pl->o->dot_scratch || pl->o->dot_scratch_bytes < gslm_dot_scratch_bytes(rows)) {
+    set_error(std::string(who) + ": dot scratch too small");
+    return GSLM_ERR_CAPACITY;
+  }
+  pl->part = (double*)pl->o->dot_scratch;
+  return GSLM_OK;
+}
+
+// FlatK over a flat param-space output y and input v (GradK views of the 7-group vectors).
+static int make_flatk(const GaussK& g, const GradK& y, const GradK& vin, const double* damp7, bool overwrite,
+                      double* dot_part, FlatK* out, bool rest_proj = false, int rest_V = 0) {
+  const int64_t R = rest_V ? 3 * rest_V : rest_proj ? 3 : 3 * (g.M - 1);
+  if (g.cov3D || g.colors || !g.raw || (g.M > 1 && y.rest_stride != R) || y.dc_stride != 3) {
+    set_error("LM gather expects raw leaves with SH colours and a flat param-space output");
     return GSLM_ERR_INVALID;
   }
-  // GSLM_MV_LEAN: opts is the base of a gslm_matvec_opts_lean; <v, y> may stay as the gather's partials (dot_defer)
-  const gslm_cg_lean* lean = (opts && (opts->flags & GSLM_MV_LEAN))
-                                 ? &reinterpret_cast<const gslm_matvec_opts_lean*>(opts)->lean : nullptr;
-  if (lean && na < 0) { set_error("matvec: GSLM_MV_LEAN is an option of gslm_matvec_view_active"); return GSLM_ERR_INVALID; }
-  const bool dot_defer = lean && lean->dot_defer;
-  const int32_t stages = (opts && opts->stages) ? opts->stages : GSLM_STAGE_ALL;
+  if (rest_proj && g.M > 1 && vin.rest && vin.rest_stride != 3) {
+    set_error("LM gather: a projected SH-rest group has 3 floats per Gaussian in v and y");
+    return GSLM_ERR_INVALID;
+  }
+  if (rest_V && g.M > 1 && vin.rest && vin.rest_stride != R) {
+    set_error("LM gather: SH-rest coordinates need 3 rest_views floats per Gaussian in v and y");
+    return GSLM_ERR_INVALID;
+  }
+  FlatK o;
+  o.y[0] = y.means3D; o.y[1] = y.dc; o.y[2] = y.rest; o.y[3] = y.scales; o.y[4] = y.rot; o.y[5] = y.opac;
+  o.v[0] = vin.means3D; o.v[1] = vin.dc; o.v[2] = vin.rest; o.v[3] = vin.scales; o.v[4] = vin.rot; o.v[5] = vin.opac;
+  // damp7 = xyz, dc, rest, scaling, rotation, opacity, exposure (GaussianModelDampMatrix order)
+  for (int k = 0; k < 6; ++k) o.damp[k] = damp7 ? (float)damp7[k] : 0.f;
+  o.use_damp = damp7 ? 1 : 0;
+  o.overwrite = overwrite ? 1 : 0;
+  o.rest_proj = (rest_proj && g.M > 1) ? 1 : 0;
+  o.rest_V = g.M > 1 ? rest_V : 0;
+  o.dot_part = dot_part;
+  if (o.use_damp || dot_part)
+    for (int k = 0; k < 6; ++k)
+      if (!o.v[k] && !(k == 2 && g.M == 1)) {
+        set_error("damping needs every group of v");
+        return GSLM_ERR_INVALID;
+      }
+  *out = o;
+  return GSLM_OK;
+}
+
+// The GATHER stage's FlatK from the plan's damp7, OVERWRITE, partials, projection and SH-rest coordinates.
+static int plan_flat(const GaussK& g, const gslm_grads* y, const gslm_grads* vin, Plan* pl) {
+  return make_flatk(g, make_gradk(y), make_gradk(vin), pl->damp7, (pl->f & F_OVERWRITE) != 0, pl->part, &pl->flat,
+                    (pl->f & F_PROJECTED) != 0, pl->rc.R ? pl->rc.V : 0);
+}
+
+// The plan of gslm_matvec_view_ex (na < 0) and gslm_matvec_view_active (na >= 0: the groups of vin, y and the fused
+// direction update hold the na Gaussians ids[0 .. na) only).  Every set_error of the two calls is here; it calls no
+// HIP function and writes nothing but *pl.
+static int plan_matvec(uint32_t entry, const gslm_matvec_opts* opts, const Bound& b, const gslm_grads* vin,
+                       const gslm_grads* y, const float* pixel_weight, bool mask_xyz, const int32_t* ids, int64_t na,
+                       const uint32_t* hrow, Plan* pl) {
+  if (!vin || !y || !pixel_weight) { set_error("matvec: NULL argument"); return GSLM_ERR_INVALID; }
+  plan_base(entry, ~0u, opts, mask_xyz, b.g.M, pl);
+  const uint32_t f = pl->f;
+  int st;
+  // (one extension struct lies behind the base: a flag's exclusions are checked before its extension is read)
+  if (excluded(f, F_DAMP_VEC) || excluded(f, E_MATVEC_EX) || excluded(f, F_EXPOSURE)) return GSLM_ERR_INVALID;
   // GSLM_MV_EXPOSURE: opts is the base of a gslm_matvec_opts_exposure; RENDER runs the product under the camera's
-  // trained exposure and sums the 12 exposure rows (checked before anything is launched)
-  const gslm_exposure_opts* expo = (opts && (opts->flags & GSLM_MV_EXPOSURE))
-                                       ? &reinterpret_cast<const gslm_matvec_opts_exposure*>(opts)->exposure : nullptr;
-  if (expo) {
-    if (lean || !mask_xyz || opts->pixel_seed || opts->jv_out || (stages & GSLM_STAGE_SCREEN) || opts->trec_in ||
-        opts->rest_basis) {
-      set_error("matvec: GSLM_MV_EXPOSURE needs mask_xyz and excludes pixel_seed, jv_out, the SCREEN stage, trec_in, "
-                "rest_basis and GSLM_MV_LEAN");
-      return GSLM_ERR_INVALID;
-    }
+  // trained exposure and sums the 12 exposure rows
+  if (f & F_EXPOSURE) {
+    const gslm_exposure_opts* expo = &reinterpret_cast<const gslm_matvec_opts_exposure*>(opts)->exposure;
     if (!expo->exposure || !expo->v_rows || !expo->y_rows || !expo->color || !expo->u_image || !expo->scratch) {
       set_error("matvec: GSLM_MV_EXPOSURE with a NULL member of gslm_exposure_opts");
       return GSLM_ERR_INVALID;
@@ -902,20 +1019,11 @@ static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gs
       set_error("matvec: GSLM_MV_EXPOSURE scratch below gslm_exposure_scratch_bytes");
       return GSLM_ERR_CAPACITY;
     }
+    pl->expo = expo;
   }
-  const double* damp7 = opts ? opts->damp7 : nullptr;
   // GSLM_MV_DAMP_VEC: opts is the base of a gslm_matvec_opts_damp; GATHER adds d (.) v with d read per element
-  // (checked before anything is launched)
-  GradK dvec{};
-  const bool use_dvec = opts && (opts->flags & GSLM_MV_DAMP_VEC);
-  if (use_dvec) {
+  if (f & F_DAMP_VEC) {
     const gslm_grads* d = reinterpret_cast<const gslm_matvec_opts_damp*>(opts)->damp_vec;
-    if (damp7 || lean || expo || !mask_xyz || opts->pixel_seed || opts->jv_out || (stages & GSLM_STAGE_SCREEN) ||
-        opts->trec_in || opts->rest_basis) {
-      set_error("matvec: GSLM_MV_DAMP_VEC needs mask_xyz and excludes damp7, pixel_seed, jv_out, the SCREEN stage, "
-                "trec_in, rest_basis, GSLM_MV_LEAN and GSLM_MV_EXPOSURE");
-      return GSLM_ERR_INVALID;
-    }
     if (!d || !d->means3D || !d->sh_dc || (b.g.M > 1 && !d->sh_rest) || !d->scales || !d->rotations || !d->opacities) {
       set_error("matvec: GSLM_MV_DAMP_VEC with a NULL damp_vec or a NULL group of it");
       return GSLM_ERR_INVALID;
@@ -924,153 +1032,144 @@ static int matvec_view(const gslm_view* view, const gslm_gaussians* gi, const gs
       set_error("matvec: GSLM_MV_DAMP_VEC: damp_vec has the groups and strides of v and y");
       return GSLM_ERR_INVALID;
     }
-    dvec = make_gradk(d);
+    pl->dvec = DampVecK{{d->means3D, d->sh_dc, d->sh_rest, d->scales, d->rotations, d->opacities}};
   }
-  double* dot_out = opts ? opts->dot_vy : nullptr;
   const bool active = na >= 0;
-  const int64_t rows = active ? na : b.g.P;  // rows of every group of vin and y
-  if (active) {
-    if (na > b.g.P || (na > 0 && (!ids || !hrow))) {
-      set_error("matvec_view_active: 0 <= n_active <= P, a non-NULL list and its row offsets");
-      return GSLM_ERR_INVALID;
-    }
-    if (!mask_xyz || !opts || !(opts->flags & GSLM_MV_TAIL_CLEAN) || (stages & GSLM_STAGE_SCREEN) || opts->trec_in) {
-      set_error("matvec_view_active: needs mask_xyz and GSLM_MV_TAIL_CLEAN (the list comes from that row map); "
-                "no SCREEN stage, no trec_in");
-      return GSLM_ERR_INVALID;
-    }
+  pl->rows = active ? na : b.g.P;
+  if (active && (na > b.g.P || (na > 0 && (!ids || !hrow)))) {
+    set_error("matvec_view_active: 0 <= n_active <= P, a non-NULL list and its row offsets");
+    return GSLM_ERR_INVALID;
   }
-  if (dot_defer && (!opts || dot_out)) {
+  if (excluded(f, E_MATVEC_ACTIVE)) return GSLM_ERR_INVALID;
+  pl->ids = ids;
+  pl->hrow = hrow;
+  pl->na = na;
+  // GSLM_MV_LEAN: opts is the base of a gslm_matvec_opts_lean; <v, y> may stay as the gather's partials (dot_defer)
+  const gslm_cg_lean* lean = (f & F_LEAN) ? &reinterpret_cast<const gslm_matvec_opts_lean*>(opts)->lean : nullptr;
+  const bool dot_defer = lean && lean->dot_defer;
+  if (dot_defer && opts->dot_vy) {
     set_error("matvec_view_active (GSLM_MV_LEAN): dot_defer leaves <v, y> as partials in dot_scratch (dot_vy must be NULL)");
     return GSLM_ERR_INVALID;
   }
-  if ((dot_out || dot_defer) && (!opts->dot_scratch || opts->dot_scratch_bytes < gslm_dot_scratch_bytes(rows))) {
-    set_error("matvec: dot scratch too small");
-    return GSLM_ERR_CAPACITY;
-  }
+  if ((st = plan_dot("matvec", pl->rows, dot_defer, pl))) return st;
   if (!b.g.raw) { set_error("matvec: gaussians must be the raw GaussianModel leaves (raw = 1)"); return GSLM_ERR_INVALID; }
-  hipStream_t s = (hipStream_t)stream;
-  b.v.stop = opts ? opts->cg_ctl : nullptr;
-  if (opts && opts->rest_basis) {
-    set_error("matvec: rest_basis is an option of gslm_tangent_views / gslm_gather_screen");
-    return GSLM_ERR_INVALID;
-  }
-  const bool proj = opts && (opts->flags & GSLM_MV_SH_REST_PROJECTED) && b.g.M > 1;
-  GaussK t = tangent_from_grads(vin, b.g, mask_xyz != 0);
-  if (proj) {
+  if (excluded(f, E_MATVEC)) return GSLM_ERR_INVALID;
+  pl->t = tangent_from_grads(vin, b.g, mask_xyz);
+  if (f & F_PROJECTED) {
     if (vin->sh_rest && vin->sh_rest_stride != 3) {
       set_error("matvec: a projected SH-rest group has 3 floats per Gaussian (sh_rest_stride 3)");
       return GSLM_ERR_INVALID;
     }
-    if (stages & GSLM_STAGE_SCREEN) {
-      set_error("matvec: GSLM_MV_SH_REST_PROJECTED is a single-view mode (no SCREEN stage)");
-      return GSLM_ERR_INVALID;
-    }
-    t.rest_proj = 1;
+    if (excluded(f, F_PROJECTED)) return GSLM_ERR_INVALID;
+    pl->t.rest_proj = 1;
   }
-  XpbyK xp{};
-  const bool fused_xpby = opts && opts->xpby_s;
-  if (fused_xpby) {
-    if (!(stages & GSLM_STAGE_TANGENT)) {
+  if (f & F_XPBY) {
+    if (!(f & F_TANGENT)) {
       set_error("matvec: xpby needs the TANGENT stage and beta_num / beta_den");
       return GSLM_ERR_INVALID;
     }
-    if ((st = build_xpby(opts, vin, proj ? 3 : 3 * (b.g.M - 1), mask_xyz != 0, &xp))) return st;
+    if ((st = build_xpby(opts, vin, (f & F_PROJECTED) ? 3 : 3 * (b.g.M - 1), mask_xyz, &pl->xp))) return st;
     if (lean && lean->beta_partials) {
       if (lean->beta_np < 0 || lean->beta_partials == opts->dot_scratch) {
         set_error("matvec_view_active (GSLM_MV_LEAN): beta's partials need a count and a buffer other than dot_scratch");
         return GSLM_ERR_INVALID;
       }
-      xp.num_part = (const double*)lean->beta_partials;
-      xp.num_np = lean->beta_np;
-      xp.num_store = lean->beta_store;
+      pl->xp.num_part = (const double*)lean->beta_partials;
+      pl->xp.num_np = lean->beta_np;
+      pl->xp.num_store = lean->beta_store;
     }
   } else if (lean && lean->beta_partials) {
     set_error("matvec_view_active (GSLM_MV_LEAN): beta's partials without the fused direction update (xpby_s)");
     return GSLM_ERR_INVALID;
   }
   // the list-order parameter block (gslm_active_params): the ACTIVE kernels read row j of it, not row ids[j] of g
-  GaussK gp = b.g;
-  const uint32_t* clamp_list = nullptr;
-  if (lean && lean->params) {
-    if (!active) { set_error("matvec_view_active (GSLM_MV_LEAN): a parameter block belongs to an active list"); return GSLM_ERR_INVALID; }
-    clamp_list = active_params_bind(lean->params, na, &gp);
-  }
-  if (opts && opts->trec_in) {
-    if (stages & GSLM_STAGE_TANGENT) {
-      set_error("matvec: trec_in replaces the TANGENT stage");
-      return GSLM_ERR_INVALID;
-    }
-    b.sb.trec = reinterpret_cast<float4*>(const_cast<float*>(opts->trec_in));
-  }
-  const float* seed = opts ? opts->pixel_seed : nullptr;
-  if (seed && (!mask_xyz || fused_xpby || (stages & (GSLM_STAGE_TANGENT | GSLM_STAGE_SCREEN)))) {
-    set_error("matvec: pixel_seed (J^T seed) needs mask_xyz and excludes TANGENT / SCREEN / xpby");
+  // (GSLM_MV_LEAN is the active entry point's, so there is a list)
+  pl->gp = b.g;
+  if (lean && lean->params) pl->clamp_list = active_params_bind(lean->params, na, &pl->gp);
+  if (excluded(f, F_TREC_IN) || excluded(f, F_SEED) || excluded(f, F_JV_OUT)) return GSLM_ERR_INVALID;
+  if ((f & F_SCREEN) && (!mask_xyz || !opts->screen_out)) {
+    set_error("matvec: GSLM_STAGE_SCREEN needs mask_xyz and opts->screen_out");
     return GSLM_ERR_INVALID;
   }
-  if ((stages & GSLM_STAGE_TANGENT) &&
-      (st = launch_tangent_pre(b.v, gp, t, nullptr, b.gb, b.sb, fused_xpby ? &xp : nullptr, s, mask_xyz != 0, ids,
-                               na, clamp_list)))
-    return st;
-  float* jv_out = opts ? opts->jv_out : nullptr;
-  if (jv_out) {
-    if (seed || (stages & (GSLM_STAGE_GATHER | GSLM_STAGE_SCREEN))) {
-      set_error("matvec: jv_out excludes pixel_seed, GATHER and SCREEN");
-      return GSLM_ERR_INVALID;
-    }
-    if (stages & GSLM_STAGE_RENDER) {
-      if (N == 0) {
-        GSLM_HIP_CHECK(hipMemsetAsync(jv_out, 0, (size_t)3 * b.v.H * b.v.W * sizeof(float), s));
-      } else if ((st = launch_render_jv(b.v, t, b.gb, b.bb, b.ib, b.sb, mask_xyz != 0, jv_out, s))) {
-        return st;
+  pl->gather = (f & F_GATHER) && !(f & (F_JV_OUT | F_SCREEN));
+  if (!pl->gather || pl->rows == 0) return GSLM_OK;
+  if ((st = plan_flat(pl->gp, y, vin, pl))) return st;
+  if (f & F_DAMP_VEC) {  // d's groups are checked above; make_flatk asks for v's with damp7 or a dot only
+    for (int k = 0; k < 6; ++k)
+      if (!pl->flat.v[k] && !(k == 2 && b.g.M == 1)) {
+        set_error("matvec: GSLM_MV_DAMP_VEC needs every group of v");
+        return GSLM_ERR_INVALID;
       }
-    }
+    pl->flat.use_damp = 1;
+  }
+  return GSLM_OK;
+}
+
+// Runs a plan of plan_matvec: up to four stages, no refusal left.
+static int run_matvec(Bound& b, const Plan& pl, const float* pixel_weight, int64_t N, void* stream) {
+  const uint32_t f = pl.f;
+  const bool mask = !(f & F_UNMASKED), tail_clean = !(f & F_TAIL_DIRTY);
+  hipStream_t s = (hipStream_t)stream;
+  int st;
+  b.v.stop = pl.stop;
+  if (f & F_TREC_IN) b.sb.trec = reinterpret_cast<float4*>(const_cast<float*>(pl.o->trec_in));
+  if ((f & F_TANGENT) && (st = launch_tangent_pre(b.v, pl.gp, pl.t, nullptr, b.gb, b.sb, (f & F_XPBY) ? &pl.xp : nullptr,
+                                                  s, mask, pl.ids, pl.na, pl.clamp_list)))
+    return st;
+  if (f & F_JV_OUT) {
+    if (!(f & F_RENDER)) return GSLM_OK;
+    if (N > 0) return launch_render_jv(b.v, pl.t, b.gb, b.bb, b.ib, b.sb, mask, pl.o->jv_out, s);
+    GSLM_HIP_CHECK(hipMemsetAsync(pl.o->jv_out, 0, (size_t)3 * b.v.H * b.v.W * sizeof(float), s));
     return GSLM_OK;
   }
-  if (seed) {
-    if ((stages & GSLM_STAGE_RENDER) &&
-        (st = launch_render_vjp_lm(b.v, b.gb, b.bb, b.ib, N, seed, b.sb, opts->flags & GSLM_MV_TAIL_CLEAN, s)))
+  const bool render = (f & F_RENDER) != 0;
+  if (render && (f & F_SEED)) {
+    if ((st = launch_render_vjp_lm(b.v, b.gb, b.bb, b.ib, N, pl.o->pixel_seed, b.sb, tail_clean, s))) return st;
+  } else if (render && (f & F_EXPOSURE)) {
+    const gslm_exposure_opts* expo = pl.expo;
+    const ExposureK ex{expo->exposure, expo->v_rows, expo->color, expo->u_image};
+    if (N > 0)
+      st = launch_matvec_render_exposure(b.v, pl.t, b.gb, b.bb, b.ib, b.sb, N, pixel_weight, ex, tail_clean, s);
+    else  // an empty list: no tile pass, J v = 0, and the exposure columns alone remain
+      st = launch_exposure_u_empty(b.v.H, b.v.W, ex.color, pixel_weight, ex.V, b.v.stop, ex.u, s);
+    if (st) return st;
+    if ((st = launch_exposure_rows(b.v.H, b.v.W, ex.color, ex.u, ex.V, (float)expo->damp, expo->overwrite != 0,
+                                   b.v.stop, (double*)expo->scratch, expo->y_rows, s)))
       return st;
-  } else if (expo) {
-    if (stages & GSLM_STAGE_RENDER) {
-      const ExposureK ex{expo->exposure, expo->v_rows, expo->color, expo->u_image};
-      if (N > 0)
-        st = launch_matvec_render_exposure(b.v, t, b.gb, b.bb, b.ib, b.sb, N, pixel_weight, ex,
-                                           (opts->flags & GSLM_MV_TAIL_CLEAN) != 0, s);
-      else  // an empty list: no tile pass, J v = 0, and the exposure columns alone remain
-        st = launch_exposure_u_empty(b.v.H, b.v.W, ex.color, pixel_weight, ex.V, b.v.stop, ex.u, s);
-      if (st) return st;
-      if ((st = launch_exposure_rows(b.v.H, b.v.W, ex.color, ex.u, ex.V, (float)expo->damp, expo->overwrite != 0,
-                                     b.v.stop, (double*)expo->scratch, expo->y_rows, s)))
-        return st;
-    }
-  } else if ((stages & GSLM_STAGE_RENDER) && N > 0 &&
-      (st = launch_matvec_render(b.v, t, b.gb, b.bb, b.ib, b.sb, N, pixel_weight, mask_xyz != 0,
-                                 opts && (opts->flags & GSLM_MV_TAIL_CLEAN), s)))
+  } else if (render && N > 0 &&
+             (st = launch_matvec_render(b.v, pl.t, b.gb, b.bb, b.ib, b.sb, N, pixel_weight, mask, tail_clean, s))) {
     return st;
-  if (stages & GSLM_STAGE_SCREEN) {
-    if (!mask_xyz || !opts->screen_out) {
-      set_error("matvec: GSLM_STAGE_SCREEN needs mask_xyz and opts->screen_out");
-      return GSLM_ERR_INVALID;
-    }
-    return launch_rowsum_screen(b.g, b.gb, b.sb, opts->screen_out, s);
   }
-  if (!(stages & GSLM_STAGE_GATHER)) return GSLM_OK;
-  double* part = (dot_out || dot_defer) ? (double*)opts->dot_scratch : nullptr;
-  if ((st = launch_gather_lm(b.v, gp, b.gb, b.sb, make_gradk(y), make_gradk(vin), damp7,
-                             (stages & GSLM_STAGE_OVERWRITE) != 0, mask_xyz != 0, part, s, proj, ids, na, hrow,
-                             clamp_list, use_dvec ? &dvec : nullptr)))
+  if (f & F_SCREEN) return launch_rowsum_screen(b.g, b.gb, b.sb, pl.o->screen_out, s);
+  if (!pl.gather) return GSLM_OK;
+  if ((st = launch_gather_lm(b.v, pl.gp, b.gb, b.sb, pl.flat, mask, s, pl.ids, pl.na, pl.hrow, pl.clamp_list,
+                             (f & F_DAMP_VEC) ? &pl.dvec : nullptr)))
     return st;
-  if (dot_out) return gslm_dot_finalize(part, (int32_t)((rows + 255) / 256), dot_out, stream);
+  if (pl.dot_out) return gslm_dot_finalize(pl.part, (int32_t)((pl.rows + 255) / 256), pl.dot_out, stream);
   return GSLM_OK;
+}
+
+// bind_all, build the plan, run the plan
+static int matvec_view(uint32_t entry, const gslm_view* view, const gslm_gaussians* gi, const gslm_grads* vin,
+                       const float* pixel_weight, int32_t mask_xyz, const void* geom, const void* binning,
+                       int64_t N, const void* image, void* scratch, size_t scratch_bytes, const gslm_grads* y,
+                       const gslm_matvec_opts* opts, const int32_t* ids, int64_t na, const uint32_t* hrow,
+                       void* stream) {
+  DebugScope dbg_scope(view != nullptr && view->debug != 0, stream);
+  Bound b;
+  Plan pl;
+  int st = bind_all(view, gi, geom, binning, N, image, scratch, scratch_bytes, &b);
+  if (st) return st;
+  if ((st = plan_matvec(entry, opts, b, vin, y, pixel_weight, mask_xyz != 0, ids, na, hrow, &pl))) return st;
+  return run_matvec(b, pl, pixel_weight, N, stream);
 }
 
 int gslm_matvec_view_ex(const gslm_view* view, const gslm_gaussians* gi, const gslm_grads* vin,
                         const float* pixel_weight, int32_t mask_xyz, const void* geom, const void* binning,
                         int64_t N, const void* image, void* scratch, size_t scratch_bytes, const gslm_grads* y,
                         const gslm_matvec_opts* opts, void* stream) {
-  return matvec_view(view, gi, vin, pixel_weight, mask_xyz, geom, binning, N, image, scratch, scratch_bytes, y, opts,
-                     nullptr, -1, nullptr, stream);
+  return matvec_view(E_MATVEC_EX, view, gi, vin, pixel_weight, mask_xyz, geom, binning, N, image, scratch, scratch_bytes,
+                     y, opts, nullptr, -1, nullptr, stream);
 }
 
 int gslm_matvec_view_active(const gslm_view* view, const gslm_gaussians* gi, const gslm_grads* vin,
@@ -1079,8 +1178,8 @@ int gslm_matvec_view_active(const gslm_view* view, const gslm_gaussians* gi, con
                             const gslm_matvec_opts* opts, const int32_t* active_ids, const uint32_t* active_rows,
                             int64_t n_active, void* stream) {
   if (n_active < 0) { set_error("matvec_view_active: negative n_active"); return GSLM_ERR_INVALID; }
-  return matvec_view(view, gi, vin, pixel_weight, mask_xyz, geom, binning, N, image, scratch, scratch_bytes, y, opts,
-                     active_ids, n_active, active_rows, stream);
+  return matvec_view(E_MATVEC_ACTIVE, view, gi, vin, pixel_weight, mask_xyz, geom, binning, N, image, scratch,
+                     scratch_bytes, y, opts, active_ids, n_active, active_rows, stream);
 }
 
 // diag(2 J^T diag(w) J [+ D]) of the matrix gslm_matvec_view_ex applies (solver_functions.py:83-132), one view
@@ -1366,17 +1465,34 @@ int gslm_rest_coords(const gslm_view* views, int32_t nviews, const gslm_gaussian
 }
 
 // opts->rest_basis of gslm_tangent_views / gslm_gather_screen: the coordinate system and this call's columns
-static int rest_opts(const char* who, const gslm_matvec_opts* opts, int32_t nviews, RestK* rc) {
-  *rc = RestK{};
-  if (!opts || !opts->rest_basis) return GSLM_OK;
+static int rest_opts(const char* who, int32_t nviews, Plan* pl) {
+  const gslm_matvec_opts* opts = pl->o;
+  if (!(pl->f & F_REST_BASIS)) return GSLM_OK;
   if (opts->rest_views < 1 || opts->rest_views > GSLM_MAX_REST_VIEWS || opts->view_base < 0 ||
       opts->view_base + nviews > opts->rest_views) {
     set_error(std::string(who) + ": rest_views outside 1..GSLM_MAX_REST_VIEWS or views past its last column");
     return GSLM_ERR_INVALID;
   }
-  rc->R = opts->rest_basis;
-  rc->V = opts->rest_views;
-  rc->view_base = opts->view_base;
+  pl->rc.R = opts->rest_basis;
+  pl->rc.V = opts->rest_views;
+  pl->rc.view_base = opts->view_base;
+  return GSLM_OK;
+}
+
+// The views of a multi-view product call, each with the solve's stop flag (a stopped solve's kernels return at once),
+// and the Gaussians, which must be the raw leaves (sh_only: with SH colours and no cov3D)
+static int bind_views(const char* who, const gslm_view* views, int32_t nviews, const gslm_gaussians* gi,
+                      const Plan& pl, bool sh_only, ViewK* vk, GaussK* g) {
+  int st;
+  for (int b = 0; b < nviews; ++b) {
+    if ((st = make_view(&views[b], gi->max_coeffs, &vk[b]))) return st;
+    vk[b].stop = pl.stop;
+  }
+  if ((st = make_gauss(gi, &vk[0], g, false))) return st;
+  if (!g->raw || (sh_only && (g->cov3D || g->colors))) {
+    set_error(std::string(who) + ": gaussians must be the raw GaussianModel leaves (raw = 1)");
+    return GSLM_ERR_INVALID;
+  }
   return GSLM_OK;
 }
 
@@ -1386,35 +1502,20 @@ int gslm_gather_screen(const gslm_view* views, int32_t nviews, const gslm_gaussi
     set_error("gather_screen: NULL argument or nviews outside 1..16");
     return GSLM_ERR_INVALID;
   }
-  if (opts && (opts->flags & GSLM_MV_DAMP_VEC)) {
-    set_error("gather_screen: GSLM_MV_DAMP_VEC is an option of gslm_matvec_view_ex / gslm_matvec_view_active");
-    return GSLM_ERR_INVALID;
-  }
+  Plan pl;
+  plan_base(E_GATHER_SCREEN, F_DAMP_VEC | F_DAMP7 | F_REST_BASIS, opts, true, 0, &pl);
+  if (excluded(pl.f, E_GATHER)) return GSLM_ERR_INVALID;
   ViewK vk[16];
   GaussK g;
   int st;
-  for (int b = 0; b < nviews; ++b) {
-    if ((st = make_view(&views[b], gi->max_coeffs, &vk[b]))) return st;
-    vk[b].stop = opts ? opts->cg_ctl : nullptr;  // a stopped solve's gather returns at once
-  }
-  if ((st = make_gauss(gi, &vk[0], &g, false))) return st;
-  if (!g.raw) { set_error("gather_screen: gaussians must be the raw GaussianModel leaves (raw = 1)"); return GSLM_ERR_INVALID; }
-  const int32_t stages = (opts && opts->stages) ? opts->stages : GSLM_STAGE_ALL;
-  const double* damp7 = opts ? opts->damp7 : nullptr;
-  double* dot_out = opts ? opts->dot_vy : nullptr;
-  if (dot_out && (!opts->dot_scratch || opts->dot_scratch_bytes < gslm_dot_scratch_bytes(g.P))) {
-    set_error("gather_screen: dot scratch too small");
-    return GSLM_ERR_CAPACITY;
-  }
-  double* part = dot_out ? (double*)opts->dot_scratch : nullptr;
+  if ((st = bind_views("gather_screen", views, nviews, gi, pl, false, vk, &g))) return st;
+  if ((st = plan_dot("gather_screen", g.P, false, &pl))) return st;
   const int64_t sstride = (opts && opts->screen_stride) ? opts->screen_stride : g.P;
   if (sstride < g.P) { set_error("gather_screen: screen_stride below P"); return GSLM_ERR_INVALID; }
-  RestK rc;
-  if ((st = rest_opts("gather_screen", opts, nviews, &rc))) return st;
-  if ((st = launch_gather_screen(vk, nviews, g, screen, sstride, make_gradk(y), make_gradk(vin), damp7,
-                                 (stages & GSLM_STAGE_OVERWRITE) != 0, part, (hipStream_t)stream, rc)))
-    return st;
-  if (dot_out) return gslm_dot_finalize(part, (int32_t)((g.P + 255) / 256), dot_out, stream);
+  if ((st = rest_opts("gather_screen", nviews, &pl))) return st;
+  if (g.P > 0 && (st = plan_flat(g, y, vin, &pl))) return st;
+  if ((st = launch_gather_screen(vk, nviews, g, screen, sstride, pl.flat, (hipStream_t)stream, pl.rc))) return st;
+  if (pl.dot_out) return gslm_dot_finalize(pl.part, (int32_t)((g.P + 255) / 256), pl.dot_out, stream);
   return GSLM_OK;
 }
 
@@ -1429,10 +1530,9 @@ static int gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t 
     set_error("gather_views: NULL argument or nviews outside 1..16");
     return GSLM_ERR_INVALID;
   }
-  if (opts && (opts->flags & GSLM_MV_DAMP_VEC)) {
-    set_error("gather_views: GSLM_MV_DAMP_VEC is an option of gslm_matvec_view_ex / gslm_matvec_view_active");
-    return GSLM_ERR_INVALID;
-  }
+  Plan pl;
+  plan_base(E_GATHER_VIEWS, F_DAMP_VEC | F_DAMP7 | F_REST_BASIS, opts, true, 0, &pl);
+  if (excluded(pl.f, E_GATHER)) return GSLM_ERR_INVALID;
   if (active && (na > gi->P || !hrow || hstride < na + 1 || fstride < na || (na > 0 && (!ids || !aflags)))) {
     set_error("gather_views_active: n_active above P, a NULL list or a stride that does not hold it");
     return GSLM_ERR_INVALID;
@@ -1443,12 +1543,7 @@ static int gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t 
   int64_t nr[MAX_SCREEN_VIEWS];
   GaussK g;
   int st;
-  for (int b = 0; b < nviews; ++b) {
-    if ((st = make_view(&views[b], gi->max_coeffs, &vk[b]))) return st;
-    vk[b].stop = opts ? opts->cg_ctl : nullptr;  // a stopped solve's gather returns at once
-  }
-  if ((st = make_gauss(gi, &vk[0], &g, false))) return st;
-  if (!g.raw) { set_error("gather_views: gaussians must be the raw GaussianModel leaves (raw = 1)"); return GSLM_ERR_INVALID; }
+  if ((st = bind_views("gather_views", views, nviews, gi, pl, false, vk, &g))) return st;
   for (int b = 0; b < nviews; ++b) {
     nr[b] = ws[b].num_rendered;
     if (nr[b] < 0 || (nr[b] > 0 && g.P > 0 && (!ws[b].geom || !ws[b].scratch))) {
@@ -1463,21 +1558,13 @@ static int gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t 
     geom_layout(g.P, const_cast<void*>(ws[b].geom), &gbs[b]);
     scratch_layout(g.P, nr[b], const_cast<void*>(ws[b].scratch), &sbs[b]);
   }
-  const int32_t stages = (opts && opts->stages) ? opts->stages : GSLM_STAGE_ALL;
-  const double* damp7 = opts ? opts->damp7 : nullptr;
-  double* dot_out = opts ? opts->dot_vy : nullptr;
-  if (dot_out && (!opts->dot_scratch || opts->dot_scratch_bytes < gslm_dot_scratch_bytes(active ? na : g.P))) {
-    set_error("gather_views: dot scratch too small");
-    return GSLM_ERR_CAPACITY;
-  }
-  double* part = dot_out ? (double*)opts->dot_scratch : nullptr;
-  RestK rc;
-  if ((st = rest_opts("gather_views", opts, nviews, &rc))) return st;
-  if ((st = launch_gather_views(vk, gbs, sbs, nr, nviews, g, make_gradk(y), make_gradk(vin), damp7,
-                                (stages & GSLM_STAGE_OVERWRITE) != 0, part, dot_out, (hipStream_t)stream, rc, ids,
-                                active ? na : -1, hrow, hstride, aflags, fstride)))
-    return st;
-  return GSLM_OK;
+  pl.rows = active ? na : g.P;
+  if ((st = plan_dot("gather_views", pl.rows, false, &pl))) return st;
+  if ((st = rest_opts("gather_views", nviews, &pl))) return st;
+  if (pl.rows > 0 && (st = plan_flat(g, y, vin, &pl))) return st;
+  pl.flat.dot_part = pl.part;  // (an empty call still finishes its dot: the sum of no partials)
+  return launch_gather_views(vk, gbs, sbs, nr, nviews, g, pl.flat, pl.dot_out, (hipStream_t)stream, pl.rc, ids,
+                             active ? na : -1, hrow, hstride, aflags, fstride);
 }
 
 int gslm_gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t nviews, const gslm_gaussians* gi,
@@ -1516,25 +1603,19 @@ static int tangent_views(const gslm_view* views, int32_t nviews, const gslm_gaus
     set_error("tangent_views_active: the LM rows (mask_xyz) and a list of at most P Gaussians");
     return GSLM_ERR_INVALID;
   }
+  Plan pl;
+  plan_base(E_TANGENT_VIEWS, F_XPBY | F_REST_BASIS, opts, mask_xyz != 0, 0, &pl);
   ViewK vk[MAX_SCREEN_VIEWS];
   GaussK g;
   int st;
-  for (int b = 0; b < nviews; ++b) {
-    if ((st = make_view(&views[b], gi->max_coeffs, &vk[b]))) return st;
-    vk[b].stop = opts ? opts->cg_ctl : nullptr;  // a stopped solve's tangent records (and direction update) are skipped
-  }
-  if ((st = make_gauss(gi, &vk[0], &g, false))) return st;
-  if (!g.raw || g.cov3D || g.colors) {
-    set_error("tangent_views: gaussians must be the raw GaussianModel leaves (raw = 1)");
-    return GSLM_ERR_INVALID;
-  }
+  if ((st = bind_views("tangent_views", views, nviews, gi, pl, true, vk, &g))) return st;
   if (g.P > 0 && (!vflags || !trec_out || flags_stride < (active ? na : g.P) || trec_stride < g.P)) {
     set_error("tangent_views: NULL vflags / trec_out or a stride below P");
     return GSLM_ERR_INVALID;
   }
   GaussK t = tangent_from_grads(vin, g, mask_xyz != 0);
-  RestK rc;
-  if ((st = rest_opts("tangent_views", opts, nviews, &rc))) return st;
+  if ((st = rest_opts("tangent_views", nviews, &pl))) return st;
+  const RestK& rc = pl.rc;
   const int R = rc.R ? 3 * rc.V : 3 * (g.M - 1);
   if (t.rest && t.rest_stride != R) {
     set_error(rc.R ? "tangent_views: SH-rest coordinates need stride 3 rest_views"
@@ -1545,10 +1626,9 @@ static int tangent_views(const gslm_view* views, int32_t nviews, const gslm_gaus
     t.rest_R = rc.R;
     t.rest_V = rc.V;
   }
-  XpbyK xp{};
-  const bool fused = opts && opts->xpby_s;
-  if (fused && (st = build_xpby(opts, vin, R, mask_xyz != 0, &xp))) return st;
-  return launch_tangent_views(vk, nviews, g, t, vflags, flags_stride, trec_out, trec_stride, fused ? &xp : nullptr,
+  const bool fused = (pl.f & F_XPBY) != 0;
+  if (fused && (st = build_xpby(opts, vin, R, mask_xyz != 0, &pl.xp))) return st;
+  return launch_tangent_views(vk, nviews, g, t, vflags, flags_stride, trec_out, trec_stride, fused ? &pl.xp : nullptr,
                               (hipStream_t)stream, mask_xyz != 0, rc.view_base, ids, active ? na : -1);
 }
 

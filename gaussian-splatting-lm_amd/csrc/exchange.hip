@@ -103,13 +103,9 @@ int launch_rowsum_screen(const GaussK& g, const GeomBufs& gb, const ScratchBufs&
 }
 
 int launch_gather_screen(const ViewK* views, int nviews, const GaussK& g, const float* screen, int64_t sstride,
-                         const GradK& y, const GradK& vin, const double* damp7, bool overwrite, double* dot_part,
-                         hipStream_t s, const RestK& rc) {
+                         const FlatK& o, hipStream_t s, const RestK& rc) {
   if (g.P == 0) return GSLM_OK;
-  FlatK o;
-  const int st = make_flatk(g, y, vin, damp7, overwrite, dot_part, &o, false, rc.R ? rc.V : 0);
-  if (st) return st;
-  if (nviews < 1 || nviews > MAX_SCREEN_VIEWS) {
+  if (nviews < 1 || nviews > MAX_SCREEN_VIEWS) {  // (gslm_gather_screen has checked it: not reachable from the C ABI)
     set_error("gather_screen: 1..16 views per call");
     return GSLM_ERR_INVALID;
   }

@@ -12,7 +12,6 @@
 #include "gslm_tile.hpp"
 #include "gslm_chain.hpp"
 #include "gslm_gather.hpp"
-#include <type_traits>
 
 namespace gslm {
 
@@ -254,69 +253,39 @@ int launch_preprocess_bwd(const ViewK& v, const GaussK& g, const GeomBufs& gb, c
   return GSLM_OK;
 }
 
-int launch_gather_lm(const ViewK& v, const GaussK& g, const GeomBufs& gb, const ScratchBufs& sb, const GradK& y,
-                     const GradK& vin, const double* damp7, bool overwrite, bool mask_xyz, double* dot_part,
-                     hipStream_t s, bool rest_proj, const int32_t* ids, int64_t na, const uint32_t* hrow,
-                     const uint32_t* clamp_list, const GradK* damp_vec) {
+int launch_gather_lm(const ViewK& v, const GaussK& g, const GeomBufs& gb, const ScratchBufs& sb, const FlatK& o,
+                     bool mask_xyz, hipStream_t s, const int32_t* ids, int64_t na, const uint32_t* hrow,
+                     const uint32_t* clamp_list, const DampVecK* dk) {
   const bool active = na >= 0;
   const int64_t nrows = active ? na : g.P;
   if (nrows == 0) return GSLM_OK;
-  FlatK o;
-  const int st = make_flatk(g, y, vin, damp7, overwrite, dot_part, &o, rest_proj);
-  if (st) return st;
+  // guards of this launcher's own contract: the C entry points' plan (api.hip plan_matvec) has checked all of it,
+  // so neither is reachable from the C ABI
   if (active && (!mask_xyz || !ids || !hrow)) {
     set_error("internal: the active-list gather runs on the LM rows (mask_xyz)");
+    return GSLM_ERR_INVALID;
+  }
+  if (dk && (!mask_xyz || !o.use_damp)) {
+    set_error("internal: the damping vector runs on the LM rows");
     return GSLM_ERR_INVALID;
   }
   const unsigned nb = (unsigned)((nrows + 255) / 256);
   const size_t rest_lds = sh_stage_floats<true>(g.M) * sizeof(float);
   const size_t chunk_lds = (size_t)GATHER_CHUNK * (mask_xyz ? 2 : 3) * sizeof(float4);
   const size_t lds = (rest_lds > chunk_lds ? rest_lds : chunk_lds) + 16;
-  if (damp_vec) {
-    // the caller (matvec_view) has checked the groups and strides of d against v's and y's
-    const GradK& d = *damp_vec;
-    const DampVecK dk{{d.means3D, d.dc, d.rest, d.scales, d.rot, d.opac}};
-    bool ok = mask_xyz && !damp7;
-    for (int k = 0; k < 6; ++k)
-      if (!(k == 2 && g.M == 1) && (!o.v[k] || !dk.d[k])) ok = false;
-    if (!ok) {
-      set_error("internal: the damping vector runs on the LM rows with every group of v and d, without damp7");
-      return GSLM_ERR_INVALID;
-    }
-    o.use_damp = 1;
-    if (active && o.rest_proj)
-      hipLaunchKernelGGL((k_gather_lm<false, 2, true, true, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw,
-                         gb.tiles, gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow, clamp_list, dk);
-    else if (active)
-      hipLaunchKernelGGL((k_gather_lm<false, 2, false, true, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw,
-                         gb.tiles, gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow, clamp_list, dk);
-    else if (o.rest_proj)
-      hipLaunchKernelGGL((k_gather_lm<false, 2, true, false, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw,
-                         gb.tiles, gb.goff, sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr, dk);
-    else
-      hipLaunchKernelGGL((k_gather_lm<false, 2, false, false, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw,
-                         gb.tiles, gb.goff, sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr, dk);
-    GSLM_LAUNCH_CHECK();
-    return GSLM_OK;
-  }
-  if (active && o.rest_proj)
-    hipLaunchKernelGGL((k_gather_lm<false, 2, true, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles,
-                       gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow, clamp_list, NoDampVec{});
-  else if (active)
-    hipLaunchKernelGGL((k_gather_lm<false, 2, false, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles,
-                       gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow, clamp_list, NoDampVec{});
-  else if (mask_xyz && o.rest_proj)
-    hipLaunchKernelGGL((k_gather_lm<false, 2, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr, NoDampVec{});
-  else if (mask_xyz)
-    hipLaunchKernelGGL((k_gather_lm<false, 2, false>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr, NoDampVec{});
-  else if (o.rest_proj)
-    hipLaunchKernelGGL((k_gather_lm<true, 3, true>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr, NoDampVec{});
-  else
-    hipLaunchKernelGGL((k_gather_lm<true, 3, false>), dim3(nb), dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff,
-                       sb.hscan, sb.contrib, o, nullptr, -1, nullptr, nullptr, NoDampVec{});
+  // the ten instantiations: the full rows (WANT_MEANS) by PROJ, the LM rows by PROJ x ACTIVE x DVEC
+  auto launch = [&](auto means, auto proj, auto act, auto dvec) {
+    constexpr bool MEANS = decltype(means)::value, DVEC = decltype(dvec)::value;
+    std::conditional_t<DVEC, DampVecK, NoDampVec> d{};
+    if constexpr (DVEC) d = *dk;
+    hipLaunchKernelGGL((k_gather_lm<MEANS, MEANS ? 3 : 2, decltype(proj)::value, decltype(act)::value, DVEC>), dim3(nb),
+                       dim3(256), lds, s, v, g, gb.clampw, gb.tiles, gb.goff, sb.hscan, sb.contrib, o, ids, na, hrow,
+                       clamp_list, d);
+  };
+  with_bool(o.rest_proj != 0, [&](auto proj) {
+    if (!mask_xyz) return launch(std::true_type{}, proj, std::false_type{}, std::false_type{});
+    with_bool(active, [&](auto act) { with_bool(dk != nullptr, [&](auto dvec) { launch(std::false_type{}, proj, act, dvec); }); });
+  });
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
 }

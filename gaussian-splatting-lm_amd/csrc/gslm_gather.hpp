@@ -7,24 +7,6 @@
 
 namespace gslm {
 
-struct FlatK {
-  float* y[6];        // xyz, dc, rest, scaling, rotation, opacity groups of the output vector
-  const float* v[6];  // same groups of the input vector (damping term)
-  float damp[6];
-  int use_damp;
-  int overwrite;
-  int rest_proj;      // GSLM_MV_SH_REST_PROJECTED: the rest group is 3 floats per Gaussian (see chain_jvp)
-  int rest_V;         // SH-rest coordinates (gslm_rest_basis): the rest group is 3 rest_V floats, staged from dsh[1..V]
-  double* dot_part;   // per-block partials of <v, y> over the written elements (NULL = off)
-};
-
-// GSLM_MV_DAMP_VEC: the damping as a vector, D = diag(d), in the groups and strides of v and y -- an argument of
-// its own (DVEC kernels only), so FlatK and the code of every other instantiation stay as they are
-struct DampVecK {
-  const float* d[6];  // xyz, dc, rest, scaling, rotation, opacity groups of d
-};
-struct NoDampVec {};
-
 // Block-cooperative version of sum_rows for the 256 consecutive Gaussians of a block: their rows are
 // one contiguous range (row_slot groups rows by Gaussian index), streamed through LDS in chunks of
 // GATHER_CHUNK rows with coalesced float4 loads; each thread then adds its own rows from LDS, in the
@@ -90,42 +72,6 @@ __device__ __forceinline__ double store_group(float* y, float d, int use_damp, i
     if (dot) acc += (double)vin[k] * (double)out;
   }
   return acc;
-}
-
-// FlatK over a flat param-space output y and input v (GradK views of the 7-group vectors).
-inline int make_flatk(const GaussK& g, const GradK& y, const GradK& vin, const double* damp7, bool overwrite,
-                      double* dot_part, FlatK* out, bool rest_proj = false, int rest_V = 0) {
-  const int64_t R = rest_V ? 3 * rest_V : rest_proj ? 3 : 3 * (g.M - 1);
-  if (g.cov3D || g.colors || !g.raw || (g.M > 1 && y.rest_stride != R) || y.dc_stride != 3) {
-    set_error("LM gather expects raw leaves with SH colours and a flat param-space output");
-    return GSLM_ERR_INVALID;
-  }
-  if (rest_proj && g.M > 1 && vin.rest && vin.rest_stride != 3) {
-    set_error("LM gather: a projected SH-rest group has 3 floats per Gaussian in v and y");
-    return GSLM_ERR_INVALID;
-  }
-  if (rest_V && g.M > 1 && vin.rest && vin.rest_stride != R) {
-    set_error("LM gather: SH-rest coordinates need 3 rest_views floats per Gaussian in v and y");
-    return GSLM_ERR_INVALID;
-  }
-  FlatK o;
-  o.y[0] = y.means3D; o.y[1] = y.dc; o.y[2] = y.rest; o.y[3] = y.scales; o.y[4] = y.rot; o.y[5] = y.opac;
-  o.v[0] = vin.means3D; o.v[1] = vin.dc; o.v[2] = vin.rest; o.v[3] = vin.scales; o.v[4] = vin.rot; o.v[5] = vin.opac;
-  // damp7 = xyz, dc, rest, scaling, rotation, opacity, exposure (GaussianModelDampMatrix order)
-  for (int k = 0; k < 6; ++k) o.damp[k] = damp7 ? (float)damp7[k] : 0.f;
-  o.use_damp = damp7 ? 1 : 0;
-  o.overwrite = overwrite ? 1 : 0;
-  o.rest_proj = (rest_proj && g.M > 1) ? 1 : 0;
-  o.rest_V = g.M > 1 ? rest_V : 0;
-  o.dot_part = dot_part;
-  if (o.use_damp || dot_part)
-    for (int k = 0; k < 6; ++k)
-      if (!o.v[k] && !(k == 2 && g.M == 1)) {
-        set_error("damping needs every group of v");
-        return GSLM_ERR_INVALID;
-      }
-  *out = o;
-  return GSLM_OK;
 }
 
 // LDS staging of a block's SH gradients.  FACTORED (one view's chain): dsh[k][ch] = shB[k] dres[ch],

@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <string>
+#include <type_traits>
 #include "gslm.h"
 #include "gslm_device.hpp"
 
@@ -46,6 +47,14 @@ int launch_failed(hipError_t e, const char* file, int line);  // sets the error 
   } while (0)
 
 inline size_t align_up(size_t x, size_t a = 256) { return (x + a - 1) / a * a; }
+
+// A run-time bool as a compile-time one: f(std::true_type{}) or f(std::false_type{}).  The launchers pick a kernel's
+// bool template arguments with it (decltype(arg)::value); only the combinations a launcher reaches are instantiated.
+template <class F>
+inline void with_bool(bool b, F&& f) {
+  if (b) f(std::true_type{});
+  else f(std::false_type{});
+}
 
 // ---------------- the CG drivers' two-pass dots (cg.hip) ----------------
 constexpr int DOT_THREADS = 256;

@@ -655,17 +655,35 @@ struct ViewsK {
   ViewK v[MAX_SCREEN_VIEWS];
   int n;
 };
+struct FlatK {
+  float* y[6];        // xyz, dc, rest, scaling, rotation, opacity groups of the output vector
+  const float* v[6];  // same groups of the input vector (damping term)
+  float damp[6];
+  int use_damp;
+  int overwrite;
+  int rest_proj;      // GSLM_MV_SH_REST_PROJECTED: the rest group is 3 floats per Gaussian (see chain_jvp)
+  int rest_V;         // SH-rest coordinates (gslm_rest_basis): the rest group is 3 rest_V floats, staged from dsh[1..V]
+  double* dot_part;   // per-block partials of <v, y> over the written elements (NULL = off)
+};
+
+// GSLM_MV_DAMP_VEC: the damping as a vector, D = diag(d), in the groups and strides of v and y -- an argument of
+// its own (DVEC kernels only), so FlatK and the code of every other instantiation stay as they are
+struct DampVecK {
+  const float* d[6];  // xyz, dc, rest, scaling, rotation, opacity groups of d
+};
+struct NoDampVec {};
+
+// the gathers take a finished FlatK: the C entry points build it (api.hip make_flatk) before anything is launched
 int launch_gather_screen(const ViewK* views, int nviews, const GaussK& g, const float* screen, int64_t sstride,
-                         const GradK& y, const GradK& vin, const double* damp7, bool overwrite, double* dot_part,
-                         hipStream_t s, const RestK& rc = RestK{});
+                         const FlatK& o, hipStream_t s, const RestK& rc = RestK{});
 // every view's head rows (the LM row maps of gbs / sbs; nr[b] <= 0: view b rendered nothing, its buffers are not read)
 // summed and chained per Gaussian in one pass (gslm_gather_views, gather_views.hip); dot_out (or NULL) = the sum of
 // the dot_part partials, left alone by a stopped solve
 int launch_gather_views(const ViewK* views, const GeomBufs* gbs, const ScratchBufs* sbs, const int64_t* nr,
-                        int nviews, const GaussK& g, const GradK& y, const GradK& vin, const double* damp7,
-                        bool overwrite, double* dot_part, double* dot_out, hipStream_t s, const RestK& rc = RestK{},
-                        const int32_t* ids = nullptr, int64_t na = -1, const uint32_t* hrow = nullptr,
-                        int64_t hstride = 0, const uint32_t* aflags = nullptr, int64_t fstride = 0);
+                        int nviews, const GaussK& g, const FlatK& o, double* dot_out, hipStream_t s,
+                        const RestK& rc = RestK{}, const int32_t* ids = nullptr, int64_t na = -1,
+                        const uint32_t* hrow = nullptr, int64_t hstride = 0, const uint32_t* aflags = nullptr,
+                        int64_t fstride = 0);
 // the union list of a view batch (gslm_active_union): nr[b] == 0 marks a view without a row map; flags [P] doubles as
 // the scan's output, scan_tmp: scan_tmp_bytes(P), total: one word; hrow [V][P + 1], aflags [V][P]
 int launch_active_union(const GeomBufs* gbs, const ScratchBufs* sbs, const int64_t* nr, int nviews, int64_t P,
@@ -702,11 +720,11 @@ int launch_exposure_u_empty(int H, int W, const float* color, const float* weigh
                             float* u, hipStream_t s);
 int launch_exposure_rows(int H, int W, const float* color, const float* u, const float* v_rows, float damp,
                          bool overwrite, const double* stop, double* part, float* y_rows, hipStream_t s);
-int launch_gather_lm(const ViewK& v, const GaussK& g, const GeomBufs& gb, const ScratchBufs& sb, const GradK& y,
-                     const GradK& vin, const double* damp7, bool overwrite, bool mask_xyz, double* dot_part,
-                     hipStream_t s, bool rest_proj = false, const int32_t* ids = nullptr, int64_t na = -1,
+// dk (or NULL): GSLM_MV_DAMP_VEC, on the LM rows with every group of v and d (o.use_damp set, o.damp unused)
+int launch_gather_lm(const ViewK& v, const GaussK& g, const GeomBufs& gb, const ScratchBufs& sb, const FlatK& o,
+                     bool mask_xyz, hipStream_t s, const int32_t* ids = nullptr, int64_t na = -1,
                      const uint32_t* hrow = nullptr, const uint32_t* clamp_list = nullptr,
-                     const GradK* damp_vec = nullptr);
+                     const DampVecK* dk = nullptr);
 // the list-order copy of what the chains load per Gaussian (gslm_active_params) and the inverse map pos [P]
 // (pos[ids[j]] = j, -1 off the list)
 int launch_active_params(const float* means3D, const float* scales, const float* rot, const float* opac,

@@ -155,6 +155,8 @@ int launch_tangent_pre(const ViewK& v, const GaussK& g, const GaussK& t, const f
   const unsigned nb = (unsigned)((n + 255) / 256) + (n == 0 ? 1u : 0u);
   XpbyK none{};
   const XpbyK& x = xp ? *xp : none;
+  // (this and the xp check below guard the launcher's own contract: the C entry points' plan -- api.hip plan_matvec,
+  // build_xpby -- has checked both, so neither is reachable from the C ABI)
   if (active && (!g.raw || m2t || (na > 0 && !ids))) {
     set_error("internal: the active-list tangent runs on raw leaves without a means2D tangent");
     return GSLM_ERR_INVALID;
@@ -243,6 +245,8 @@ int launch_tangent_views(const ViewK* views, int nviews, const GaussK& g, const 
   const bool active = na >= 0;
   const int64_t n = active ? na : g.P;
   if (n == 0 && !(xp && xp->tail_p)) return GSLM_OK;  // an empty shard with a tail: one block updates it
+  // (the two internal checks guard the launcher's own contract: tangent_views and build_xpby in api.hip have checked
+  // both, so neither is reachable from the C ABI)
   if (xp && t.rest && (t.rest != xp->p[2] || t.rest_stride != xp->w[2])) {
     set_error("internal: fused xpby expects the tangent's SH-rest group to be p's");
     return GSLM_ERR_INVALID;

@@ -326,6 +326,11 @@ int gslm_matvec_view(const gslm_view* view, const gslm_gaussians* g, const gslm_
  * along Bh = B_rest / |B_rest| (the same operator on the 3(M-1) -> 3 coordinates of that span; convert with
  * gslm_sh_rest_project).  Not for the SCREEN stage (multi-view). */
 #define GSLM_MV_SH_REST_PROJECTED 2
+/* The options of the product entry points: gslm_matvec_view_ex, gslm_matvec_view_active, gslm_gather_screen,
+ * gslm_gather_views (_active) and gslm_tangent_views (_active).
+ * Error contract, for all of them: every GSLM_ERR_INVALID or GSLM_ERR_CAPACITY return precedes the call's first
+ * launch and leaves every caller buffer untouched -- y, v (the fused direction update's p) and x, jv_out, screen_out,
+ * the dot and its scratch, the exposure rows, and the scratch workspace.  Only GSLM_ERR_HIP can follow a launch. */
 typedef struct gslm_matvec_opts {
   int32_t stages;         /* GSLM_STAGE_* bits; 0 means GSLM_STAGE_ALL (accumulate) */
   int32_t flags;          /* GSLM_MV_* bits */

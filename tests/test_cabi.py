@@ -91,6 +91,47 @@ def test_invalid_arguments_return_error_codes():
     assert b"rest_views" in lib.gslm_last_error()
 
 
+def test_product_options_are_refused_before_any_device_work():
+    """The product entry points refuse a combination of options from the flags, the stages and the pointers alone: with
+    P = 0 no device memory stands behind the call, and no GPU is there to launch on (a call that got as far as a launch
+    would return GSLM_ERR_HIP)."""
+    from gslm import _lib
+    lib = _lib.lib
+    INV, CAP = _lib.GSLM_ERR_INVALID, _lib.GSLM_ERR_CAPACITY
+    FAKE = 4096  # a non-NULL pointer that is never followed
+    view = _lib.make_view(64, 64, 0.5, 0.5, [0, 0, 0], 1.0, [0.0] * 16, [0.0] * 16, 0, [0, 0, 0])
+    g = _lib.make_gaussians(0)
+    g.raw = 1
+    v = _lib.GslmGrads()
+    v.sh_dc_stride = 3
+
+    def ex(mask_xyz=1, **fields):
+        o = _lib.GslmMatvecOpts()
+        for k, val in fields.items():
+            setattr(o, k, val)
+        return lib.gslm_matvec_view_ex(ctypes.byref(view), ctypes.byref(g), ctypes.byref(v), FAKE, mask_xyz, None, None, 0,
+                                       None, None, 1 << 20, ctypes.byref(v), ctypes.byref(o), None)
+
+    cases = [("jv_out with the default stages (GATHER among them)", INV, dict(jv_out=FAKE)),
+             ("SCREEN without screen_out", INV, dict(stages=1 | 2 | 16)),
+             ("SCREEN without mask_xyz", INV, dict(stages=1 | 2 | 16, screen_out=FAKE, mask_xyz=0)),
+             ("pixel_seed with TANGENT", INV, dict(pixel_seed=FAKE)),
+             ("trec_in with TANGENT", INV, dict(trec_in=FAKE)),
+             ("rest_basis", INV, dict(rest_basis=FAKE, rest_views=1)),
+             ("GSLM_MV_LEAN on gslm_matvec_view_ex", INV, dict(flags=4)),
+             ("GSLM_MV_DAMP_VEC with GSLM_MV_EXPOSURE", INV, dict(flags=16 | 8)),
+             ("dot_vy without its scratch", CAP, dict(dot_vy=FAKE))]
+    for what, want, kw in cases:
+        assert ex(**kw) == want, what
+        assert lib.gslm_last_error(), what
+    views = (_lib.GslmView * 2)(view, view)
+    o = _lib.GslmMatvecOpts()
+    o.flags = 16
+    assert lib.gslm_gather_screen(views, 2, ctypes.byref(g), FAKE, ctypes.byref(v), ctypes.byref(v), ctypes.byref(o),
+                                  None) == INV
+    assert b"GSLM_MV_DAMP_VEC" in lib.gslm_last_error()
+
+
 def test_union_binning_argument_checks():
     """The line search's shared binning (ABI 8; ABI 9 adds each set workspace's size and n_sets): set counts outside
     1..8, slots outside [0, n_sets), set workspaces below gslm_depth_records_bytes(P), NULL workspaces and short buffers
