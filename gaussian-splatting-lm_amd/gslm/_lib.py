@@ -508,6 +508,25 @@ def _host_floats(t, n):
     return [float(x) for x in list(t)][:n]
 
 
+# The same rule for anything derived from a tensor's contents and kept (a depth order of xyz, a list-order copy of the
+# leaves, "this is the right-hand side I produced"): a token is the tensor object itself and its version counter.  It
+# matches only that object at that version.  Holding the object is what makes the address safe to leave out: while the
+# token lives the allocator cannot hand the storage to another tensor, and a new tensor that happens to land where a
+# freed one was (optimizer surgery builds fresh Parameters at version 0) is another object.  An alias (t.detach(), a
+# view) shares the storage and the counter but is another object too, and misses: callers pass the tensor itself.
+def tensor_token(t):
+    return (t, t._version)
+
+
+def token_matches(tok, t):
+    return tok is not None and tok[0] is t and tok[1] == t._version
+
+
+def tokens_match(toks, ts):
+    """A tuple of tokens against as many tensors: every one matches."""
+    return toks is not None and len(toks) == len(ts) and all(token_matches(k, t) for k, t in zip(toks, ts))
+
+
 def make_view(H, W, tanfovx, tanfovy, bg, scale_modifier, viewmatrix, projmatrix, sh_degree, campos,
               prefiltered=False, antialiasing=False, debug=False):
     v = GslmView()

@@ -115,12 +115,13 @@ class ViewRaster:
         """(block, pos): the list-order copy of the parameters the LM chains load per Gaussian (gslm_active_params)
         for active_list(), and the inverse map pos [P] (list row of a Gaussian, -1 off the list).  The block is a
         snapshot of the leaves, so it is keyed on them: built with the list (a forward or backward drops both) and
-        again whenever a leaf was replaced or written in place since (storage address and version counter), which
-        is checked here at every use -- a solve never reads a block older than its parameters."""
+        again whenever a leaf was replaced or written in place since (the tensor objects and their version counters:
+        _lib.tensor_token), which is checked here at every use -- a solve never reads a block older than its
+        parameters."""
         ids, na = self.active_list(P, stream)
         leaves = (model._xyz, model._scaling, model._rotation, model._opacity)
-        key = tuple((t.data_ptr(), t._version) for t in leaves)
-        if self._params is None or self._params[0] != key:
+        if self._params is None or not _lib.tokens_match(self._params[0], leaves):
+            key = tuple(_lib.tensor_token(t) for t in leaves)
             dev = self.device
             block = _lib.u8(lib.gslm_active_params_bytes(na), dev)
             pos = torch.empty(max(P, 1), dtype=torch.int32, device=dev)
@@ -531,7 +532,7 @@ class LMProblem(_ProductOpts):
     def _mark_rhs(self, out, fused=True):
         """Remember the J^T b this problem produced (exposure slice zeroed): cgls_fused may then skip the exposure
         slice's D v in every product without checking it (exposure_is_zero)."""
-        self._rhs_token = (out.data_ptr(), out._version)
+        self._rhs_token = _lib.tensor_token(out)
         # (the fused gather's J^T b is zero off the view's active list by construction: zero_off_active)
         self._rhs_epochs = [vr.epoch for vr in self.views] if fused else None
         return out
@@ -548,8 +549,8 @@ class LMProblem(_ProductOpts):
         return not bool(g[e0:e1].any())
 
     def rhs_is_mine(self, g):
-        """g is the J^T b this problem's rhs() produced, unmodified since."""
-        return getattr(self, "_rhs_token", None) == (g.data_ptr(), g._version)
+        """g is the J^T b this problem's rhs() produced -- that tensor object itself -- unmodified since."""
+        return _lib.token_matches(getattr(self, "_rhs_token", None), g)
 
     def rhs_full(self, out):
         """J^T b through the drop-in gslm_backward, in the reference's layout (full_layout)."""
@@ -1886,11 +1887,12 @@ class LossEvaluator:
         return None if m is None else m.data_ptr()
 
     def _refresh_orders(self, xyz, P):
-        """Drop the cached depth orders (and their inverses) when xyz moved: another tensor, version or size."""
-        key = (xyz.data_ptr(), xyz._version, P)
-        if key != self._order_key:
+        """Drop the cached depth orders (and their inverses) when xyz moved: another tensor object, version or size
+        (_lib.tensor_token: the key holds xyz, so no later tensor can take its address while the orders live)."""
+        key = self._order_key
+        if key is None or key[1] != P or not _lib.token_matches(key[0], xyz):
             V = len(self.views)
-            self._order_key, self._orders = key, [None] * V
+            self._order_key, self._orders = (_lib.tensor_token(xyz), P), [None] * V
             self._pos = [None] * V
 
     def _preprocess_ordered(self, i, g, geom, sh):

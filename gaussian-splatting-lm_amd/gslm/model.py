@@ -241,6 +241,9 @@ class _FirstOrder:
                                      None if max_r is None else max_r.data_ptr(),
                                      self.xyz_gradient_accum.data_ptr(), self.denom.data_ptr(),
                                      stream_handle(g.device)), "gslm_densify_stats")
+        # (written through their data pointers: the version bump an in-place torch op would have given them)
+        torch.autograd.graph.increment_version(
+            [self.xyz_gradient_accum, self.denom] + ([] if max_r is None else [max_r]))
 
 
 def get_expon_lr_func(lr_init, lr_final, lr_delay_steps=0, lr_delay_mult=1.0, max_steps=1000000):

@@ -47,13 +47,19 @@ class FusedAdam(torch.optim.Adam):
             state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
         return state
 
-    def _launch(self, descs, betas, eps, visible=None, num_gaussians=0):
-        for i in range(0, len(descs), _lib.ADAM_MAX_GROUPS):
-            chunk = descs[i:i + _lib.ADAM_MAX_GROUPS]
-            arr = (_lib.GslmAdamGroup * len(chunk))(*chunk)
+    def _launch(self, items, betas, eps, visible=None, num_gaussians=0):
+        """gslm_adam_step over `items`, (descriptor, (parameter, state)) pairs.  The kernel writes the parameter and
+        both moments through their data pointers, which autograd does not see: each launch is followed by the version
+        bump torch.optim.Adam's in-place ops give the same tensors, so whatever was derived from the old values (a
+        saved tensor of a graph not yet run backward, a cached depth order keyed on the version) is known stale."""
+        for i in range(0, len(items), _lib.ADAM_MAX_GROUPS):
+            chunk = items[i:i + _lib.ADAM_MAX_GROUPS]
+            arr = (_lib.GslmAdamGroup * len(chunk))(*[d for d, _ in chunk])
             check(lib.gslm_adam_step(arr, len(chunk), float(betas[0]), float(betas[1]), float(eps),
                                      None if visible is None else visible.data_ptr(), int(num_gaussians),
                                      0 if visible is None else 1, _lib.stream_handle()), "gslm_adam_step")
+            torch.autograd.graph.increment_version(
+                [t for _, (p, state) in chunk for t in (p, state["exp_avg"], state["exp_avg_sq"])])
 
     @staticmethod
     def _desc(p, state, lr, step=0, per_gauss=1):
@@ -84,7 +90,7 @@ class FusedAdam(torch.optim.Adam):
                 by_hyper.setdefault(key, []).append(
                     (self._desc(p, state, group["lr"], step=int(state["step"].item())), (p, state)))
         for (betas, eps), items in by_hyper.items():
-            self._launch([d for d, _ in items], betas, eps)
+            self._launch(items, betas, eps)
         return loss
 
 
@@ -113,8 +119,8 @@ class SparseGaussianAdam(FusedAdam):
                 raise ValueError(f"SparseGaussianAdam: group '{group.get('name')}' has {p.numel()} floats, "
                                  f"not a multiple of N = {N}")
             state = self._state(p)
-            by_eps.setdefault(group["eps"], []).append(self._desc(p, state, group["lr"],
-                                                                  per_gauss=p.numel() // max(N, 1)))
+            by_eps.setdefault(group["eps"], []).append(
+                (self._desc(p, state, group["lr"], per_gauss=p.numel() // max(N, 1)), (p, state)))
         # the upstream kernel hard-codes b1 = 0.9, b2 = 0.999 and takes the group's lr and eps
-        for eps, descs in by_eps.items():
-            self._launch(descs, (0.9, 0.999), eps, visible=vis, num_gaussians=N)
+        for eps, items in by_eps.items():
+            self._launch(items, (0.9, 0.999), eps, visible=vis, num_gaussians=N)
