@@ -411,7 +411,7 @@ size_t gslm_loss_scratch_bytes(int32_t H, int32_t W) {
 static int rasterize_loss(const gslm_view* view, int64_t P, void* geom, void* binning, size_t binning_bytes, int64_t N,
                           const float* gt, const float* alpha_mask, const float* exposure, bool want_exposure,
                           void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate, void* stream,
-                          const gslm_robust* robust = nullptr) {
+                          const gslm_robust* robust = nullptr, const DepthLossK* depth = nullptr) {
   bool rob = false;
   gslm_robust rb{};
   int st = robust_arg(robust, "rasterize_loss_robust", &rob, &rb);
@@ -420,6 +420,7 @@ static int rasterize_loss(const gslm_view* view, int64_t P, void* geom, void* bi
   st = make_view(view, 1, &v);
   if (st) return st;
   if (want_exposure && !exposure) { set_error("rasterize_loss_exposure: NULL exposure"); return GSLM_ERR_INVALID; }
+  if (depth && !depth->gt) { set_error("rasterize_loss_depth: NULL invdepth_gt"); return GSLM_ERR_INVALID; }
   if (binning_bytes < gslm_binning_bytes(N, v.H, v.W)) { set_error("binning workspace too small"); return GSLM_ERR_CAPACITY; }
   if (scratch_bytes < gslm_loss_scratch_bytes(v.H, v.W)) { set_error("loss scratch too small"); return GSLM_ERR_CAPACITY; }
   if (!gt || !loss_dev || !scratch) { set_error("rasterize_loss: NULL gt / loss / scratch"); return GSLM_ERR_INVALID; }
@@ -430,7 +431,28 @@ static int rasterize_loss(const gslm_view* view, int64_t P, void* geom, void* bi
   hipStream_t s = (hipStream_t)stream;
   if ((st = launch_binning(v, P, gb, bb, N, s))) return st;
   return launch_render_loss(v, gb, bb, gt, alpha_mask, (double*)scratch, loss_dev, accumulate ? 1 : 0, s, nullptr, 0,
-                            nullptr, exposure, rob ? &rb : nullptr);
+                            nullptr, exposure, rob ? &rb : nullptr, depth);
+}
+
+// depth_weight checked (finite, >= 0) into the loss blends' block
+static int depth_loss_arg(const char* who, const float* invdepth_gt, const float* depth_mask, double depth_weight,
+                          DepthLossK* out) {
+  if (!(depth_weight >= 0.0) || !std::isfinite(depth_weight)) {
+    set_error(std::string(who) + ": depth_weight must be finite and >= 0");
+    return GSLM_ERR_INVALID;
+  }
+  *out = DepthLossK{invdepth_gt, depth_mask, 0.5 * depth_weight};
+  return GSLM_OK;
+}
+
+int gslm_rasterize_loss_depth(const gslm_view* view, int64_t P, void* geom, void* binning, size_t binning_bytes,
+                              int64_t N, const float* gt, const float* alpha_mask, const float* invdepth_gt,
+                              const float* depth_mask, double depth_weight, void* scratch, size_t scratch_bytes,
+                              double* loss_dev, int32_t accumulate, void* stream) {
+  DepthLossK dl;
+  if (int st = depth_loss_arg("rasterize_loss_depth", invdepth_gt, depth_mask, depth_weight, &dl)) return st;
+  return rasterize_loss(view, P, geom, binning, binning_bytes, N, gt, alpha_mask, nullptr, false, scratch,
+                        scratch_bytes, loss_dev, accumulate, stream, nullptr, &dl);
 }
 
 int gslm_rasterize_loss_robust(const gslm_view* view, int64_t P, void* geom, void* binning, size_t binning_bytes,
@@ -563,7 +585,7 @@ static int rasterize_loss_slot(const gslm_view* view, int64_t P, const void* geo
                                const void* binning, size_t binning_bytes, int64_t N, int32_t slot, int32_t n_sets,
                                const float* gt, const float* alpha_mask, const float* exposure, bool want_exposure,
                                void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate,
-                               void* stream, const gslm_robust* robust = nullptr) {
+                               void* stream, const gslm_robust* robust = nullptr, const DepthLossK* depth = nullptr) {
   bool rob = false;
   gslm_robust rb{};
   int st = robust_arg(robust, "rasterize_loss_slot_robust", &rob, &rb);
@@ -571,6 +593,7 @@ static int rasterize_loss_slot(const gslm_view* view, int64_t P, const void* geo
   ViewK v;
   st = make_view(view, 1, &v);
   if (st) return st;
+  if (depth && !depth->gt) { set_error("rasterize_loss_slot_depth: NULL invdepth_gt"); return GSLM_ERR_INVALID; }
   if (want_exposure && !exposure) { set_error("rasterize_loss_slot_exposure: NULL exposure"); return GSLM_ERR_INVALID; }
   if (n_sets < 1 || n_sets > MAX_UNION_SETS || slot < 0 || slot >= n_sets) {
     set_error("rasterize_loss_slot: need 0 <= slot < n_sets <= 8");
@@ -590,7 +613,18 @@ static int rasterize_loss_slot(const gslm_view* view, int64_t P, const void* geo
   union_masks_layout(N, v.gx * v.gy, const_cast<void*>(binning), &um);
   return launch_render_loss(v, gb, bb, gt, alpha_mask, (double*)scratch, loss_dev, accumulate ? 1 : 0,
                             (hipStream_t)stream, N > 0 ? um.sorted : nullptr, 4 * slot, um.nsets, exposure,
-                            rob ? &rb : nullptr);
+                            rob ? &rb : nullptr, depth);
+}
+
+int gslm_rasterize_loss_slot_depth(const gslm_view* view, int64_t P, const void* geom, size_t set_bytes,
+                                   const void* binning, size_t binning_bytes, int64_t N, int32_t slot, int32_t n_sets,
+                                   const float* gt, const float* alpha_mask, const float* invdepth_gt,
+                                   const float* depth_mask, double depth_weight, void* scratch, size_t scratch_bytes,
+                                   double* loss_dev, int32_t accumulate, void* stream) {
+  DepthLossK dl;
+  if (int st = depth_loss_arg("rasterize_loss_slot_depth", invdepth_gt, depth_mask, depth_weight, &dl)) return st;
+  return rasterize_loss_slot(view, P, geom, set_bytes, binning, binning_bytes, N, slot, n_sets, gt, alpha_mask, nullptr,
+                             false, scratch, scratch_bytes, loss_dev, accumulate, stream, nullptr, &dl);
 }
 
 int gslm_rasterize_loss_slot_robust(const gslm_view* view, int64_t P, const void* geom, size_t set_bytes,
@@ -871,6 +905,7 @@ enum : uint32_t {
   F_TANGENT = 1u << 15, F_RENDER = 1u << 16, F_GATHER = 1u << 17, F_SCREEN = 1u << 18, F_OVERWRITE = 1u << 19,
   F_UNMASKED = 1u << 20,    // mask_xyz = 0
   F_TAIL_DIRTY = 1u << 21,  // no GSLM_MV_TAIL_CLEAN
+  F_DEPTH = 1u << 22,       // GSLM_MV_DEPTH
 };
 // Which go together, once: a call in `mode` with any of `excludes` is refused (GSLM_ERR_INVALID).
 static const struct { uint32_t mode, excludes; const char* msg; } kExcludes[] = {
@@ -891,6 +926,9 @@ static const struct { uint32_t mode, excludes; const char* msg; } kExcludes[] = 
     {F_SEED, F_UNMASKED | F_XPBY | F_TANGENT | F_SCREEN,
      "matvec: pixel_seed (J^T seed) needs mask_xyz and excludes TANGENT / SCREEN / xpby"},
     {F_JV_OUT, F_SEED | F_GATHER | F_SCREEN, "matvec: jv_out excludes pixel_seed, GATHER and SCREEN"},
+    {F_DEPTH, F_UNMASKED | F_EXPOSURE | F_DAMP_VEC | F_JV_OUT | F_SCREEN | E_GATHER | E_TANGENT_VIEWS,
+     "GSLM_MV_DEPTH is an option of gslm_matvec_view_ex / gslm_matvec_view_active on the LM rows (mask_xyz); it "
+     "excludes GSLM_MV_EXPOSURE, GSLM_MV_DAMP_VEC, jv_out and the SCREEN stage"},
 };
 static bool excluded(uint32_t f, uint32_t mode) {
   for (const auto& r : kExcludes)
@@ -930,6 +968,7 @@ static void plan_base(uint32_t entry, uint32_t accepts, const gslm_matvec_opts* 
                (st & GSLM_STAGE_GATHER ? F_GATHER : 0) | (st & GSLM_STAGE_SCREEN ? F_SCREEN : 0) |
                (st & GSLM_STAGE_OVERWRITE ? F_OVERWRITE : 0) | (fl & GSLM_MV_LEAN ? F_LEAN : 0) |
                (fl & GSLM_MV_EXPOSURE ? F_EXPOSURE : 0) | (fl & GSLM_MV_DAMP_VEC ? F_DAMP_VEC : 0) |
+               (fl & GSLM_MV_DEPTH ? F_DEPTH : 0) |
                ((fl & GSLM_MV_SH_REST_PROJECTED) && M > 1 ? F_PROJECTED : 0) | (fl & GSLM_MV_TAIL_CLEAN ? 0 : F_TAIL_DIRTY) |
                (mask_xyz ? 0 : F_UNMASKED);
   if (o) f |= (o->pixel_seed ? F_SEED : 0) | (o->jv_out ? F_JV_OUT : 0) | (o->trec_in ? F_TREC_IN : 0) |
@@ -1006,7 +1045,8 @@ static int plan_matvec(uint32_t entry, const gslm_matvec_opts* opts, const Bound
   const uint32_t f = pl->f;
   int st;
   // (one extension struct lies behind the base: a flag's exclusions are checked before its extension is read)
-  if (excluded(f, F_DAMP_VEC) || excluded(f, E_MATVEC_EX) || excluded(f, F_EXPOSURE)) return GSLM_ERR_INVALID;
+  if (excluded(f, F_DEPTH) || excluded(f, F_DAMP_VEC) || excluded(f, E_MATVEC_EX) || excluded(f, F_EXPOSURE))
+    return GSLM_ERR_INVALID;
   // GSLM_MV_EXPOSURE: opts is the base of a gslm_matvec_opts_exposure; RENDER runs the product under the camera's
   // trained exposure and sums the 12 exposure rows
   if (f & F_EXPOSURE) {
@@ -1124,7 +1164,9 @@ static int run_matvec(Bound& b, const Plan& pl, const float* pixel_weight, int64
   }
   const bool render = (f & F_RENDER) != 0;
   if (render && (f & F_SEED)) {
-    if ((st = launch_render_vjp_lm(b.v, b.gb, b.bb, b.ib, N, pl.o->pixel_seed, b.sb, tail_clean, s))) return st;
+    if ((st = launch_render_vjp_lm(b.v, b.gb, b.bb, b.ib, N, pl.o->pixel_seed, b.sb, tail_clean, s,
+                                   (f & F_DEPTH) != 0)))
+      return st;
   } else if (render && (f & F_EXPOSURE)) {
     const gslm_exposure_opts* expo = pl.expo;
     const ExposureK ex{expo->exposure, expo->v_rows, expo->color, expo->u_image};
@@ -1137,7 +1179,8 @@ static int run_matvec(Bound& b, const Plan& pl, const float* pixel_weight, int64
                                    b.v.stop, (double*)expo->scratch, expo->y_rows, s)))
       return st;
   } else if (render && N > 0 &&
-             (st = launch_matvec_render(b.v, pl.t, b.gb, b.bb, b.ib, b.sb, N, pixel_weight, mask, tail_clean, s))) {
+             (st = launch_matvec_render(b.v, pl.t, b.gb, b.bb, b.ib, b.sb, N, pixel_weight, mask, tail_clean, s,
+                                        (f & F_DEPTH) != 0))) {
     return st;
   }
   if (f & F_SCREEN) return launch_rowsum_screen(b.g, b.gb, b.sb, pl.o->screen_out, s);
@@ -1503,8 +1546,8 @@ int gslm_gather_screen(const gslm_view* views, int32_t nviews, const gslm_gaussi
     return GSLM_ERR_INVALID;
   }
   Plan pl;
-  plan_base(E_GATHER_SCREEN, F_DAMP_VEC | F_DAMP7 | F_REST_BASIS, opts, true, 0, &pl);
-  if (excluded(pl.f, E_GATHER)) return GSLM_ERR_INVALID;
+  plan_base(E_GATHER_SCREEN, F_DAMP_VEC | F_DAMP7 | F_REST_BASIS | F_DEPTH, opts, true, 0, &pl);
+  if (excluded(pl.f, E_GATHER) || excluded(pl.f, F_DEPTH)) return GSLM_ERR_INVALID;
   ViewK vk[16];
   GaussK g;
   int st;
@@ -1531,8 +1574,8 @@ static int gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t 
     return GSLM_ERR_INVALID;
   }
   Plan pl;
-  plan_base(E_GATHER_VIEWS, F_DAMP_VEC | F_DAMP7 | F_REST_BASIS, opts, true, 0, &pl);
-  if (excluded(pl.f, E_GATHER)) return GSLM_ERR_INVALID;
+  plan_base(E_GATHER_VIEWS, F_DAMP_VEC | F_DAMP7 | F_REST_BASIS | F_DEPTH, opts, true, 0, &pl);
+  if (excluded(pl.f, E_GATHER) || excluded(pl.f, F_DEPTH)) return GSLM_ERR_INVALID;
   if (active && (na > gi->P || !hrow || hstride < na + 1 || fstride < na || (na > 0 && (!ids || !aflags)))) {
     set_error("gather_views_active: n_active above P, a NULL list or a stride that does not hold it");
     return GSLM_ERR_INVALID;
@@ -1604,7 +1647,8 @@ static int tangent_views(const gslm_view* views, int32_t nviews, const gslm_gaus
     return GSLM_ERR_INVALID;
   }
   Plan pl;
-  plan_base(E_TANGENT_VIEWS, F_XPBY | F_REST_BASIS, opts, mask_xyz != 0, 0, &pl);
+  plan_base(E_TANGENT_VIEWS, F_XPBY | F_REST_BASIS | F_DEPTH, opts, mask_xyz != 0, 0, &pl);
+  if (excluded(pl.f, F_DEPTH)) return GSLM_ERR_INVALID;
   ViewK vk[MAX_SCREEN_VIEWS];
   GaussK g;
   int st;

@@ -52,6 +52,43 @@ __global__ __launch_bounds__(256, 8) void k_render_bwd(ViewK v, const uint2* __r
                                         rec, slots, rect, goff, s_rp, s_bits, s_acc, s_misc, rows);
 }
 
+// k_render_bwd<false, false, 2> seeded with a fourth plane, dL/d(inverse depth) (GSLM_MV_DEPTH): the LM rows of a
+// J^T b with a depth residual.  vjp_tile's "seed only" form: the rows and the LDS are those of the plain kernel.
+__global__ __launch_bounds__(256, 8) void k_render_bwd_lm_depth(ViewK v, const uint2* __restrict__ ranges,
+                                                              const uint32_t* __restrict__ tile_order,
+                                                              const uint32_t* __restrict__ point_list,
+                                                              const float4* __restrict__ rec,
+                                                              const uint32_t* __restrict__ slots,
+                                                              const uint2* __restrict__ rect,
+                                                              const uint32_t* __restrict__ goff,
+                                                              const float* __restrict__ final_T,
+                                                              const uint32_t* __restrict__ n_contrib,
+                                                              const float* __restrict__ seed4,
+                                                              float4* __restrict__ rows) {
+  constexpr int B = 128;
+  __shared__ float2 s_rp[5 * B];
+  __shared__ uint64_t s_bits[16];
+  __shared__ float s_acc[vjp_acc_floats<false, false, B>()];
+  __shared__ int s_misc[4];
+  const TilePix p = tile_pix(v, tile_order);
+  const int64_t pid = p.pid;
+  const int64_t HW = (int64_t)v.H * v.W;
+  float d0 = 0.f, d1 = 0.f, d2 = 0.f, di = 0.f, Tf = 0.f;
+  uint32_t last = 0;
+  if (p.inside) {
+    d0 = seed4[pid];
+    d1 = seed4[HW + pid];
+    d2 = seed4[2 * HW + pid];
+    di = seed4[3 * HW + pid];
+    Tf = final_T[pid];
+    last = n_contrib[pid];
+  }
+  VjpPix st;
+  vjp_init(st, v, p.inside, Tf, last, d0, d1, d2, di);
+  vjp_tile<false, false, 2, B, true>(st, (float)p.px, (float)p.py, p.tile_x, p.tile_y, ranges[p.tile], point_list, rec,
+                                     slots, rect, goff, s_rp, s_bits, s_acc, s_misc, rows);
+}
+
 // ---------------------------------------------------------------- launchers
 int launch_render_bwd(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const ImgBufs& ib, int64_t N,
                       const float* dL_dcolor, const float* dL_dinv, const ScratchBufs& sb, hipStream_t s) {
@@ -75,16 +112,21 @@ int launch_render_bwd(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, con
 }
 
 int launch_render_vjp_lm(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const ImgBufs& ib, int64_t N,
-                         const float* dL_dcolor, const ScratchBufs& sb, bool tail_clean, hipStream_t s) {
+                         const float* dL_dcolor, const ScratchBufs& sb, bool tail_clean, hipStream_t s, bool depth) {
   const int ntiles = v.gx * v.gy;
   if (N == 0) return GSLM_OK;
   if (!tail_clean) {  // the LM row map: once per geometry, shared with k_render_matvec
     const int st = launch_lm_rowmap(v, gb, bb, ib, sb, N, s);
     if (st) return st;
   }
-  hipLaunchKernelGGL((k_render_bwd<false, false, 2>), dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges, bb.tile_order,
-                     bb.point_list, gb.rec, bb.slots, gb.rect, gb.goff, ib.final_T, ib.n_contrib, dL_dcolor, nullptr,
-                     sb.contrib);  // head rows only (launch_lm_rowmap)
+  if (depth)  // dL_dcolor is [4, H, W]: the fourth plane seeds the inverse depth
+    hipLaunchKernelGGL(k_render_bwd_lm_depth, dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges, bb.tile_order,
+                       bb.point_list, gb.rec, bb.slots, gb.rect, gb.goff, ib.final_T, ib.n_contrib, dL_dcolor,
+                       sb.contrib);
+  else
+    hipLaunchKernelGGL((k_render_bwd<false, false, 2>), dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges,
+                       bb.tile_order, bb.point_list, gb.rec, bb.slots, gb.rect, gb.goff, ib.final_T, ib.n_contrib,
+                       dL_dcolor, nullptr, sb.contrib);  // head rows only (launch_lm_rowmap)
   GSLM_LAUNCH_CHECK();
   return GSLM_OK;
 }

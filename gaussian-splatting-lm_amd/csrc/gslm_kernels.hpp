@@ -559,11 +559,17 @@ int robust_arg(const gslm_robust* robust, const char* what, bool* on, gslm_robus
 // amask (or NULL): the blend visits by the union list's per-set masks (bits `shift` .. shift + 3 of amask[k],
 // k_duplicate_union) with the records of gb (that set's geometry) instead of the point list's own quadrant bits;
 // exposure (or NULL): the camera's 12 device floats, applied to the final colour before the clamp;
-// robust (or NULL; never with exposure): a checked HUBER / CAUCHY block, the per-tile sum then takes robust_rho
+// robust (or NULL; never with exposure): a checked HUBER / CAUCHY block, the per-tile sum then takes robust_rho;
+// depth (or NULL; never with exposure or robust): the inverse-depth block's term after the pixel's colour terms
+struct DepthLossK {
+  const float* gt;     // the inverse-depth target [H, W]
+  const float* mask;   // the depth mask [H, W], or NULL (= 1)
+  double half_weight;  // depth_weight / 2: the final pass doubles the tile sums
+};
 int launch_render_loss(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const float* gt, const float* mask,
                        double* part, double* loss, int accumulate, hipStream_t s, const uint32_t* amask = nullptr,
                        int shift = 0, const uint32_t* nsets = nullptr, const float* exposure = nullptr,
-                       const gslm_robust* robust = nullptr);
+                       const gslm_robust* robust = nullptr, const DepthLossK* depth = nullptr);
 // ---- the line search's shared binning (forward.hip, gslm_union_*) ----
 constexpr int MAX_UNION_SETS = 8;  // 4 mask bits per set in one uint32 per list entry
 struct UnionSets {
@@ -609,7 +615,8 @@ namespace gslm {
 int launch_render_bwd(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const ImgBufs& ib, int64_t N,
                       const float* dL_dcolor, const float* dL_dinv, const ScratchBufs& sb, hipStream_t s);
 int launch_render_vjp_lm(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const ImgBufs& ib, int64_t N,
-                         const float* dL_dcolor, const ScratchBufs& sb, bool tail_clean, hipStream_t s);
+                         const float* dL_dcolor, const ScratchBufs& sb, bool tail_clean, hipStream_t s,
+                         bool depth = false);  // depth (GSLM_MV_DEPTH): dL_dcolor is [4, H, W], plane 3 seeds 1/z
 int launch_preprocess_bwd(const ViewK& v, const GaussK& g, const GeomBufs& gb, const BinBufs& bb,
                           const ScratchBufs& sb, const GradK& out, bool want_means, hipStream_t s);
 // Fused CG direction update run by the tangent kernel before it reads the direction: every
@@ -703,7 +710,7 @@ int launch_render_jv(const ViewK& v, const GaussK& t, const GeomBufs& gb, const 
                      const ScratchBufs& sb, bool mask_xyz, float* jv_out, hipStream_t s);
 int launch_matvec_render(const ViewK& v, const GaussK& t, const GeomBufs& gb, const BinBufs& bb, const ImgBufs& ib,
                          const ScratchBufs& sb, int64_t N, const float* weight, bool mask_xyz, bool tail_clean,
-                         hipStream_t s);
+                         hipStream_t s, bool depth = false);  // depth (GSLM_MV_DEPTH, mask_xyz): weight is [4, H, W]
 // The LM product under a trained per-camera exposure (GSLM_MV_EXPOSURE): X, V = the camera's exposure and the
 // direction's exposure rows (12 device floats each, row-major [3][4]), color = the forward's raw render, u = the
 // [3,H,W] image the tile pass leaves for the exposure rows' reduction (residual.hip).

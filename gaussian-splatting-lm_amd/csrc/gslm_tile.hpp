@@ -408,7 +408,10 @@ constexpr int vjp_acc_floats() { return 4 * n_used<WITH_XY, WITH_INV>() * acc_st
 // written.  slots != NULL (the LM row map): rows exist for those head entries only.  slots == NULL (the drop-in's
 // rectangle rows): the caller fills every row with zeros first (launch_render_bwd).
 // s_rp: the batch's five record planes (stage_entry), 5 BATCH float2.
-template <bool WITH_XY, bool WITH_INV, int ROWF4, int BATCH>
+// SEED_INV (the LM rows' depth residual, WITH_INV false): st.dinv seeds dL/dalpha through <1/z, dinv> -- with xyz
+// frozen a Gaussian's 1/z is a constant, so the depth term has columns through alpha only and no row value of its
+// own (NU and the row format are those without it).
+template <bool WITH_XY, bool WITH_INV, int ROWF4, int BATCH, bool SEED_INV = false>
 __device__ __forceinline__ void vjp_tile(VjpPix& st, float pxf, float pyf, int tile_x, int tile_y,
                                          uint2 range, const uint32_t* __restrict__ point_list,
                                          const float4* __restrict__ rec, const uint32_t* __restrict__ slots,
@@ -462,7 +465,7 @@ __device__ __forceinline__ void vjp_tile(VjpPix& st, float pxf, float pyf, int t
         {
 #pragma clang fp contract(fast)
           cd = (e.rg.x * st.dpix[0] + e.rg.y * st.dpix[1]) + e.bd.x * st.dpix[2];
-          if (WITH_INV) cd += e.bd.y * st.dinv;
+          if (WITH_INV || SEED_INV) cd += e.bd.y * st.dinv;
         }
         // A visit some lane blends runs the body in every lane, an invalid lane with alpha = G = 0: its row
         // values are 0, T is unchanged (rcp(1) = 1) and its accumulation update adds 0 * (...).  No per-lane

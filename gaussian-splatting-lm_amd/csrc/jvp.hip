@@ -111,9 +111,12 @@ __device__ __forceinline__ void jvp_tile(JvpPix& o, bool inside, float pxf, floa
 // [dop dr dg db] -- which the hit loop reads with one address register; the tangent conic carries its power
 // factors (da' = -da / 2, db' = -db, dc' = -dc / 2).  A lane blends position pos only while pos < its own n_contrib
 // (my_last): the skip and stop decisions are the primal's.
+// DEPTH (k_render_matvec_depth): the record's 1/z is staged as a fifth, float plane sd (64 floats, the wave's own) and
+// the visit adds dD += 1/z dw.  With xyz frozen 1/z has no tangent: the inverse depth moves through alpha only.
+template <bool DEPTH = false>
 __device__ __forceinline__ void jvp_wave_packed(JvpPix& o, float pxf, float pyf, uint32_t my_last, int wm, int q,
                                                 const uint32_t* __restrict__ pl, const float4* __restrict__ rec,
-                                                const float4* __restrict__ trec, float4* s) {
+                                                const float4* __restrict__ trec, float4* s, float* sd = nullptr) {
   const int lane = threadIdx.x & 63;
   o.T = 1.f;
   o.dT = 0.f;
@@ -133,6 +136,7 @@ __device__ __forceinline__ void jvp_wave_packed(JvpPix& o, float pxf, float pyf,
         s[64 + lane] = r1;
         s[128 + lane] = make_float4(r2.x, -0.5f * c0.x, -c0.y, -0.5f * c0.z);  // blue, da', db', dc'
         s[192 + lane] = make_float4(c0.w, c1.x, c1.y, c1.z);                    // dopacity, dr, dg, db
+        if constexpr (DEPTH) sd[lane] = r2.y;                                   // 1/z
       }
     }
     uint64_t hb = __ballot(hit);
@@ -146,6 +150,11 @@ __device__ __forceinline__ void jvp_wave_packed(JvpPix& o, float pxf, float pyf,
       const float4 a = s[j], b = s[64 + j], C = s[128 + j], D = s[192 + j];
       asm volatile("" : : "v"(b.z), "v"(b.w), "v"(C.x), "v"(C.y), "v"(C.z), "v"(C.w), "v"(D.x), "v"(D.y), "v"(D.z),
                    "v"(D.w));
+      float invz = 0.f;
+      if constexpr (DEPTH) {
+        invz = sd[j];
+        asm volatile("" : : "v"(invz));  // with the record's other loads
+      }
       const float dx = a.x - pxf, dy = a.y - pyf;
       const float power = gpower(a.z, a.w, b.x, dx, dy);
       const float G = gexp(power);
@@ -160,6 +169,7 @@ __device__ __forceinline__ void jvp_wave_packed(JvpPix& o, float pxf, float pyf,
         o.dC[0] = fmaf(b.z, dw, fmaf(D.y, wt, o.dC[0]));
         o.dC[1] = fmaf(b.w, dw, fmaf(D.z, wt, o.dC[1]));
         o.dC[2] = fmaf(C.x, dw, fmaf(D.w, wt, o.dC[2]));
+        if constexpr (DEPTH) o.dD = fmaf(invz, dw, o.dD);
         o.dT = o.dT * (1.f - alpha) - o.T * dalpha;
         o.T = o.T * (1.f - alpha);
       }
@@ -170,14 +180,19 @@ __device__ __forceinline__ void jvp_wave_packed(JvpPix& o, float pxf, float pyf,
 
 // jvp_wave_packed for the thread's wave on its own quadrant of tile p: the wave's bound (the largest n_contrib of its
 // pixels, `last` being 0 outside the image; clamped by the range length as wave_bounds' n_eff is) and its 256 float4
-// of the 4 x 256 at s_rec.
+// of the 4 x 256 at s_rec.  DEPTH: and its 64 floats of the 1/z plane behind them (s_rec + 1024: 4 x 64 floats).
+template <bool DEPTH = false>
 __device__ __forceinline__ void jvp_wave_quadrant(JvpPix& o, const TilePix& p, uint32_t last, uint2 range,
                                                   const uint32_t* __restrict__ point_list,
                                                   const float4* __restrict__ rec, const float4* __restrict__ trec,
                                                   float4* s_rec) {
   const int q = threadIdx.x >> 6;
   const int wm = __builtin_amdgcn_readfirstlane(min(wave_max_u((int)last), (int)(range.y - range.x)));
-  jvp_wave_packed(o, (float)p.px, (float)p.py, last, wm, q, point_list + range.x, rec, trec, s_rec + 256 * q);
+  if constexpr (DEPTH)
+    jvp_wave_packed<true>(o, (float)p.px, (float)p.py, last, wm, q, point_list + range.x, rec, trec, s_rec + 256 * q,
+                          reinterpret_cast<float*>(s_rec + 4 * 256) + 64 * q);
+  else
+    jvp_wave_packed(o, (float)p.px, (float)p.py, last, wm, q, point_list + range.x, rec, trec, s_rec + 256 * q);
 }
 
 // J v only, compact LM records, one independent wave per quadrant (jvp_wave_packed).
@@ -379,6 +394,40 @@ __global__ __launch_bounds__(256, 8) void k_render_matvec_exposure(
                                     rect, goff, Lds::planes(s_lds), s_bits, Lds::acc(s_lds), Lds::misc(s_lds), contrib);
 }
 
+// k_render_matvec<false> with an inverse-depth residual (GSLM_MV_DEPTH): weight is [4, H, W], its fourth plane
+// w3 = lambda_d m_d^2.  The J v pass carries dD = sum 1/z dw (jvp_wave_packed<true>; the inverse depth has no background
+// term), u3 = w3 dD -- the depth block enters the loss once: no factor 2 -- seeds the back-to-front pass's dinv, and
+// vjp_tile's "seed only" form folds <1/z, u3> into dL/dalpha.  The LM rows, the row map and the LDS (the 1/z plane
+// lies in the 224 float4 between the J v pass's records and kVjp) are k_render_matvec<false>'s; with w3 = 0 so are
+// the rows' bits (cd + 1/z 0 = cd).
+__global__ __launch_bounds__(256, 8) void k_render_matvec_depth(
+    ViewK v, const uint2* __restrict__ ranges, const uint32_t* __restrict__ tile_order,
+    const uint32_t* __restrict__ point_list, const float4* __restrict__ rec, const float4* __restrict__ trec,
+    const uint32_t* __restrict__ slots, const uint2* __restrict__ rect, const uint32_t* __restrict__ goff,
+    const float* __restrict__ final_T, const uint32_t* __restrict__ n_contrib, const float* __restrict__ weight,
+    float4* __restrict__ contrib) {
+  using Lds = MatvecLds<false>;
+  static_assert(Lds::kFloat4 >= 4 * 256 + 64, "the 1/z plane fits behind the J v pass's records");
+  __shared__ uint64_t s_bits[16];
+  __shared__ float4 s_lds[Lds::kFloat4];
+  if (cg_stopped(v)) return;
+  const TilePix p = tile_pix(v, tile_order);
+  const uint2 range = ranges[p.tile];
+  const MatvecPix m = load_matvec_pix(v, p, final_T, n_contrib, weight);
+  const float w3 = p.inside ? weight[3 * ((int64_t)v.H * v.W) + p.pid] : 0.f;
+  JvpPix o;
+  jvp_wave_quadrant<true>(o, p, m.last, range, point_list, rec, trec, s_lds);
+  const float u0 = 2.f * m.w0 * (o.dC[0] + o.dT * v.bg[0]);
+  const float u1 = 2.f * m.w1 * (o.dC[1] + o.dT * v.bg[1]);
+  const float u2 = 2.f * m.w2 * (o.dC[2] + o.dT * v.bg[2]);
+  const float u3 = w3 * o.dD;
+  VjpPix st;
+  vjp_init(st, v, p.inside, m.Tf, m.last, u0, u1, u2, u3);
+  vjp_tile<false, false, 2, Lds::B, true>(st, (float)p.px, (float)p.py, p.tile_x, p.tile_y, range, point_list, rec,
+                                          slots, rect, goff, Lds::planes(s_lds), s_bits, Lds::acc(s_lds),
+                                          Lds::misc(s_lds), contrib);
+}
+
 // ------------------------------------------------------------------ launchers
 int launch_jvp(const ViewK& v, const GaussK& g, const GaussK& t, const float* m2t, const GeomBufs& gb,
                const BinBufs& bb, const ImgBufs& ib, const ScratchBufs& sb, float* out_color_t, float* out_inv_t,
@@ -412,14 +461,18 @@ int launch_render_jv(const ViewK& v, const GaussK& t, const GeomBufs& gb, const 
 
 int launch_matvec_render(const ViewK& v, const GaussK& t, const GeomBufs& gb, const BinBufs& bb, const ImgBufs& ib,
                          const ScratchBufs& sb, int64_t N, const float* weight, bool mask_xyz, bool tail_clean,
-                         hipStream_t s) {
+                         hipStream_t s, bool depth) {
   const int ntiles = v.gx * v.gy;
   // the LM row map (head entries only; ScratchBufs::hscan): computed by the first product on a geometry
   if (!tail_clean) {
     const int st = launch_lm_rowmap(v, gb, bb, ib, sb, N, s);
     if (st) return st;
   }
-  if (mask_xyz)
+  if (depth && mask_xyz)
+    hipLaunchKernelGGL(k_render_matvec_depth, dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges, bb.tile_order,
+                       bb.point_list, gb.rec, sb.trec, bb.slots, gb.rect, gb.goff, ib.final_T, ib.n_contrib, weight,
+                       sb.contrib);
+  else if (mask_xyz)
     hipLaunchKernelGGL(k_render_matvec<false>, dim3(ntiles), dim3(TILE_PIX), 0, s, v, bb.ranges, bb.tile_order, bb.point_list,
                        gb.rec, sb.trec, bb.slots, gb.rect, gb.goff, ib.final_T, ib.n_contrib, weight,
                        sb.contrib);

@@ -25,7 +25,12 @@ enum { FWD_FULL = 0, FWD_NO_INV = 1, FWD_LOSS = 2 };
 // (k_slot_masks: the set's own quadrant mask, 0 outside the set's rect) instead of the point list's.
 // EXPO: loss_term<true> through the camera's exposure map X (12 device floats, wave-uniform, read after the loop).
 // ROBUST (never with EXPO): loss_term's robust form with the block rb.
-template <int MODE, bool SLOT = false, bool EXPO = false, bool ROBUST = false>
+// DEPTH (the plain loss only; gslm_rasterize_loss_depth and its slot form): the loop also accumulates the inverse depth
+// Dp exactly as FWD_FULL does, and after the three colour terms, in their order, the pixel adds the depth block's term
+// (gslm_lm_residual_depth's r, in its order): r = m_d (Dp - Dgt), dl.half_weight ((double) r (double) r) -- half the
+// weight, since the final pass doubles every tile sum (the [r; r] aliasing, which the depth block does not have; the
+// halving and the doubling are exact).
+template <int MODE, bool SLOT = false, bool EXPO = false, bool ROBUST = false, bool DEPTH = false>
 __global__ __launch_bounds__(256) void k_render_fwd_wave(ViewK v, const uint2* __restrict__ ranges,
                                                           const uint32_t* __restrict__ tile_order,
                                                           const uint32_t* __restrict__ point_list,
@@ -34,8 +39,10 @@ __global__ __launch_bounds__(256) void k_render_fwd_wave(ViewK v, const uint2* _
                                                           uint32_t* __restrict__ n_contrib, const float* __restrict__ gt,
                                                           const float* __restrict__ mask, double* __restrict__ part,
                                                           const uint32_t* __restrict__ amask, int shift,
-                                                          const float* __restrict__ X, gslm_robust rb) {
+                                                          const float* __restrict__ X, gslm_robust rb,
+                                                          DepthLossK dl) {
   static_assert(!EXPO || MODE == FWD_LOSS, "the exposure map belongs to the loss epilogue");
+  static_assert(!DEPTH || (MODE == FWD_LOSS && !EXPO && !ROBUST), "the depth term belongs to the plain loss epilogue");
   static_assert(!ROBUST || (MODE == FWD_LOSS && !EXPO), "the robust loss belongs to the plain loss epilogue");
   __shared__ float4 s_rec[4][3 * 64];
   const TilePix p = tile_pix(v, tile_order);
@@ -69,7 +76,7 @@ __global__ __launch_bounds__(256) void k_render_fwd_wave(ViewK v, const uint2* _
       const HitRec h = load_hit<true>(s, j);
       float wt;
       const bool stop = fwd_visit(h, pxf, pyf, st, wt);
-      if (MODE == FWD_FULL) Dp = __builtin_fmaf(h.c.y, wt, Dp);
+      if (MODE == FWD_FULL || DEPTH) Dp = __builtin_fmaf(h.c.y, wt, Dp);
       if (MODE != FWD_LOSS) last = wt > 0.0f ? (uint32_t)(base + j + 1) : last;  // blended: 1-based list position
       // the stop compare's lane mask (no VGPR round trip) leaves `live`; the round ends when no lane is
       live_update(live, hb, __builtin_amdgcn_ballot_w64(stop));
@@ -94,6 +101,11 @@ __global__ __launch_bounds__(256) void k_render_fwd_wave(ViewK v, const uint2* _
       }
 #pragma unroll
       for (int c = 0; c < 3; ++c) acc += loss_term<EXPO, ROBUST>(R, x, c, m, gtc[c], rb);
+      if constexpr (DEPTH) {
+        const float md = dl.mask ? dl.mask[pid] : 1.0f;
+        const float r = md * (Dp - dl.gt[pid]);
+        acc += dl.half_weight * ((double)r * (double)r);
+      }
     }
     const double sum = block_sum4(acc, s_sum);
     if (tid == 0) part[p.tile] = sum;
@@ -293,12 +305,13 @@ struct FwdArgs {
   int shift = 0;
   const float* X = nullptr;
   gslm_robust rb{};
+  DepthLossK dl{};
 };
-template <int MODE, bool SLOT = false, bool EXPO = false, bool ROBUST = false>
+template <int MODE, bool SLOT = false, bool EXPO = false, bool ROBUST = false, bool DEPTH = false>
 static void launch_fwd(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const FwdArgs& a, hipStream_t s) {
-  hipLaunchKernelGGL((k_render_fwd_wave<MODE, SLOT, EXPO, ROBUST>), dim3(v.gx * v.gy), dim3(TILE_PIX), 0, s, v,
+  hipLaunchKernelGGL((k_render_fwd_wave<MODE, SLOT, EXPO, ROBUST, DEPTH>), dim3(v.gx * v.gy), dim3(TILE_PIX), 0, s, v,
                      bb.ranges, bb.tile_order, bb.point_list, gb.rec, a.out_color, a.out_invdepth, a.final_T,
-                     a.n_contrib, a.gt, a.mask, a.part, a.amask, a.shift, a.X, a.rb);
+                     a.n_contrib, a.gt, a.mask, a.part, a.amask, a.shift, a.X, a.rb, a.dl);
 }
 
 int launch_render_fwd(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const ImgBufs& ib, float* out_color,
@@ -317,14 +330,15 @@ int launch_render_fwd(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, con
 
 int launch_render_loss(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, const float* gt, const float* mask,
                        double* part, double* loss, int accumulate, hipStream_t s, const uint32_t* amask, int shift,
-                       const uint32_t* nsets, const float* exposure, const gslm_robust* robust) {
+                       const uint32_t* nsets, const float* exposure, const gslm_robust* robust,
+                       const DepthLossK* depth) {
   const int ntiles = v.gx * v.gy;
   if (ntiles == 0) {
     if (!accumulate) GSLM_HIP_CHECK(hipMemsetAsync(loss, 0, sizeof(double), s));
     return GSLM_OK;
   }
-  if (exposure && robust) {
-    set_error("rasterize_loss: no exposure x robust form");
+  if ((exposure && robust) || (depth && (exposure || robust))) {
+    set_error("rasterize_loss: no exposure x robust, depth x exposure or depth x robust form");
     return GSLM_ERR_INVALID;
   }
   FwdArgs a;
@@ -335,7 +349,10 @@ int launch_render_loss(const ViewK& v, const GeomBufs& gb, const BinBufs& bb, co
   a.shift = shift;
   a.X = exposure;
   if (robust) a.rb = *robust;
-  if (robust && amask) launch_fwd<FWD_LOSS, true, false, true>(v, gb, bb, a, s);
+  if (depth) a.dl = *depth;
+  if (depth && amask) launch_fwd<FWD_LOSS, true, false, false, true>(v, gb, bb, a, s);
+  else if (depth) launch_fwd<FWD_LOSS, false, false, false, true>(v, gb, bb, a, s);
+  else if (robust && amask) launch_fwd<FWD_LOSS, true, false, true>(v, gb, bb, a, s);
   else if (robust) launch_fwd<FWD_LOSS, false, false, true>(v, gb, bb, a, s);
   else if (exposure && amask) launch_fwd<FWD_LOSS, true, true>(v, gb, bb, a, s);
   else if (exposure) launch_fwd<FWD_LOSS, false, true>(v, gb, bb, a, s);

@@ -15,6 +15,7 @@
 // The float expressions follow the torch ones in gslm/lm.py's reference restatement operation by
 // operation, so r, w and seed are bit-identical to it.
 #include <algorithm>
+#include <cmath>
 
 #include "gslm_kernels.hpp"
 
@@ -70,6 +71,44 @@ __global__ __launch_bounds__(RES_THREADS) void k_lm_loss_final(const double* __r
   }
 }
 
+// ---- the inverse-depth block (gslm_lm_residual_depth; the reference's Ll1depth_per_pixel slot, as a least-squares
+// block that enters the loss once) ----
+// Per pixel p, D = the rendered inverse depth (no background term, no clamp), g = its target, m = the depth mask
+// (1 when absent), lam = (float)depth_weight:
+//   r     = m * (D - g)                 one subtraction, one product
+//   w     = lam * (m * m)               weight of J_D^T W_d J_D
+//   seed  = -w * r                      (-w) * r: the negation is exact; dL/dD of J^T b
+//   loss += (double)depth_weight * ((double)r * (double)r)      per pixel; block partials, then k_lm_depth_loss_final
+// in this order, uncontracted.  With a mask of zeros and ones -w r = -lam m^2 (D - g), the right-hand side's term.
+__global__ __launch_bounds__(RES_THREADS) void k_lm_residual_depth(int64_t HW, const float* __restrict__ invdepth,
+                                                                   const float* __restrict__ gt,
+                                                                   const float* __restrict__ mask, float lam,
+                                                                   double lam_d, float* __restrict__ residual,
+                                                                   float* __restrict__ weight, float* __restrict__ seed,
+                                                                   double* __restrict__ part) {
+  __shared__ double s[RES_THREADS / 64];
+  double acc = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * RES_THREADS;
+  for (int64_t p = (int64_t)blockIdx.x * RES_THREADS + threadIdx.x; p < HW; p += stride) {
+    const float m = mask ? mask[p] : 1.0f;
+    const float r = m * (invdepth[p] - gt[p]);
+    const float w = lam * (m * m);
+    if (residual) residual[p] = r;
+    if (weight) weight[p] = w;
+    if (seed) seed[p] = (-w) * r;
+    acc += lam_d * ((double)r * (double)r);
+  }
+  const double sum = block_sum4(acc, s);
+  if (threadIdx.x == 0) part[blockIdx.x] = sum;
+}
+
+// k_lm_loss_final without the [r; r] factor: the depth block enters the loss once
+__global__ __launch_bounds__(RES_THREADS) void k_lm_depth_loss_final(const double* __restrict__ part, int np,
+                                                                     int accumulate, double* __restrict__ loss) {
+  __shared__ double s[RES_THREADS / 64];
+  const double sum = block_sum4(strided_sum_in_order(part, np), s);
+  if (threadIdx.x == 0) *loss = accumulate ? *loss + sum : sum;
+}
 
 // ---- the same epilogue under a trained per-camera exposure (gaussian_renderer/__init__.py:113-119) ----
 // X = the camera's 3x4 exposure, row-major [i][k].  Per pixel, R the raw render:
@@ -270,6 +309,29 @@ int gslm_lm_residual_robust(int32_t H, int32_t W, const float* color, const floa
                             size_t scratch_bytes, double* loss_dev, int32_t accumulate, void* stream) {
   return lm_residual(H, W, color, gt, alpha_mask, robust, residual, weight, seed, scratch, scratch_bytes, loss_dev,
                      accumulate, stream);
+}
+
+int gslm_lm_residual_depth(int32_t H, int32_t W, const float* invdepth, const float* invdepth_gt,
+                           const float* depth_mask, double depth_weight, float* residual, float* weight, float* seed,
+                           void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate, void* stream) {
+  if (H < 0 || W < 0) { set_error("lm_residual_depth: negative image size"); return GSLM_ERR_INVALID; }
+  const int64_t HW = (int64_t)H * W;
+  if (HW > 0 && (!invdepth || !invdepth_gt)) { set_error("lm_residual_depth: NULL invdepth / invdepth_gt"); return GSLM_ERR_INVALID; }
+  if (!(depth_weight >= 0.0) || !std::isfinite(depth_weight)) {
+    set_error("lm_residual_depth: depth_weight must be finite and >= 0");
+    return GSLM_ERR_INVALID;
+  }
+  if (!loss_dev || !scratch) { set_error("lm_residual_depth: NULL loss or scratch"); return GSLM_ERR_INVALID; }
+  if (scratch_bytes < gslm_residual_scratch_bytes(H, W)) { set_error("lm_residual_depth: scratch too small"); return GSLM_ERR_CAPACITY; }
+  hipStream_t s = (hipStream_t)stream;
+  const int nb = (int)std::min<int64_t>(1024, std::max<int64_t>(1, (HW + RES_THREADS - 1) / RES_THREADS));
+  double* part = (double*)scratch;
+  hipLaunchKernelGGL(k_lm_residual_depth, dim3(nb), dim3(RES_THREADS), 0, s, HW, invdepth, invdepth_gt, depth_mask,
+                     (float)depth_weight, depth_weight, residual, weight, seed, part);
+  GSLM_LAUNCH_CHECK();
+  hipLaunchKernelGGL(k_lm_depth_loss_final, dim3(1), dim3(RES_THREADS), 0, s, part, nb, accumulate ? 1 : 0, loss_dev);
+  GSLM_LAUNCH_CHECK();
+  return GSLM_OK;
 }
 
 

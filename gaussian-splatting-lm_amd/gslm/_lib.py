@@ -361,6 +361,21 @@ EXPORTS = {
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
                                                ctypes.c_int32, ctypes.c_void_p]),
+    "gslm_lm_residual_depth": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p,
+                                              ctypes.c_void_p, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p,
+                                              ctypes.c_int32, ctypes.c_void_p]),
+    "gslm_rasterize_loss_depth": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int64, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64, ctypes.c_void_p,
+                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
+                                                 ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int32,
+                                                 ctypes.c_void_p]),
+    "gslm_rasterize_loss_slot_depth": (ctypes.c_int, [ctypes.POINTER(GslmView), ctypes.c_int64, ctypes.c_void_p,
+                                                      ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int64,
+                                                      ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
+                                                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
+                                                      ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_int32,
+                                                      ctypes.c_void_p]),
     "gslm_exposure_scratch_bytes": (ctypes.c_size_t, [ctypes.c_int32, ctypes.c_int32]),
     "gslm_lm_residual_exposure": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p,
                                                  ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,

@@ -83,7 +83,10 @@ class Camera:
         # cameras.py:46-49 -- an all-ones mask when the image has no alpha channel
         self.alpha_mask = (alpha_mask.to(device) if alpha_mask is not None
                            else torch.ones_like(self.original_image[0:1]))
+        # cameras.py:60-78 -- the mono-depth target: [1,H,W] inverse depth, the pixels it holds for ([1,H,W], None = all)
+        # and whether the camera has one at all (the depth residual of gslm.lm reads all three)
         self.invdepthmap = None
+        self.depth_mask = None
         self.depth_reliable = False
         self.zfar = 100.0
         self.znear = 0.01
@@ -101,6 +104,9 @@ class Camera:
         for name in ("original_image", "alpha_mask", "world_view_transform", "projection_matrix",
                      "full_proj_transform", "camera_center"):
             setattr(self, name, getattr(self, name).to(device))
+        for name in ("invdepthmap", "depth_mask"):
+            if getattr(self, name) is not None:
+                setattr(self, name, getattr(self, name).to(device))
         return self
 
 

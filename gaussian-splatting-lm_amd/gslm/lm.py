@@ -34,6 +34,7 @@ MV_SH_REST_PROJECTED = 2  # GSLM_MV_SH_REST_PROJECTED
 MV_LEAN = 4  # GSLM_MV_LEAN
 MV_EXPOSURE = 8  # GSLM_MV_EXPOSURE
 MV_DAMP_VEC = 16  # GSLM_MV_DAMP_VEC
+MV_DEPTH = 32  # GSLM_MV_DEPTH
 DIAG_TAIL_CLEAN = 1  # gslm_lm_diag_view flags: GSLM_DIAG_TAIL_CLEAN
 DIAG_ACCUMULATE = 2  # GSLM_DIAG_ACCUMULATE
 DIAG_SH_REST_PROJECTED = 4  # GSLM_DIAG_SH_REST_PROJECTED
@@ -311,12 +312,55 @@ def _robust_struct(robust):
     return None if robust is None else _lib.GslmRobust(_ROBUST_KINDS[robust[0]], robust[1])
 
 
+def depth_option(depth_weight):
+    """The `depth_weight` option of LMProblem checked: None (no depth residual), or a finite number >= 0 -- returned as
+    None or a float; ValueError otherwise."""
+    if depth_weight is None:
+        return None
+    ok = isinstance(depth_weight, (int, float)) and not isinstance(depth_weight, bool)
+    if not ok or not (math.isfinite(depth_weight) and depth_weight >= 0):
+        raise ValueError(f"depth_weight must be None or a finite number >= 0, got {depth_weight!r}")
+    return float(depth_weight)
+
+
+def _depth_plane(t, what, H, W, device):
+    """A depth target or mask checked: float32 [1, H, W] (ValueError otherwise), contiguous on `device`."""
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (1, H, W):
+        got = (t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__
+        raise ValueError(f"{what} must be float32 [1, {H}, {W}], got {got}")
+    return t.to(device).contiguous()
+
+
+def depth_targets(cams, invdepths, depth_masks, device):
+    """Per camera (target, mask) of the depth residual, or None for a camera without one.  invdepths / depth_masks:
+    explicit lists (as gts / alpha_masks; a None target: no depth term for that view, a None mask: every pixel), or
+    None for the cameras' own fields -- invdepthmap where depth_reliable is set, and depth_mask."""
+    if invdepths is not None and len(invdepths) != len(cams):
+        raise ValueError(f"invdepths: one entry per camera ({len(cams)}), got {len(invdepths)}")
+    if depth_masks is not None and len(depth_masks) != len(cams):
+        raise ValueError(f"depth_masks: one entry per camera ({len(cams)}), got {len(depth_masks)}")
+    out = []
+    for b, c in enumerate(cams):
+        if invdepths is not None:
+            gt = invdepths[b]
+        else:
+            gt = c.invdepthmap if getattr(c, "depth_reliable", False) else None
+        m = depth_masks[b] if depth_masks is not None else getattr(c, "depth_mask", None)
+        if gt is None:
+            out.append(None)
+            continue
+        H, W = c.image_height, c.image_width
+        out.append((_depth_plane(gt, "an inverse-depth target", H, W, device),
+                    None if m is None else _depth_plane(m, "a depth mask", H, W, device)))
+    return out
+
+
 class LMProblem(_ProductOpts):
     """The LM normal equations of one camera batch (one LM step's worth of cached geometry)."""
 
     def __init__(self, model, cams, bg, gts=None, alpha_masks=None, mask_xyz=True, damp=None, device="cuda",
                  ssim=False, lambda_dssim=0.2, sh_projection=False, train_exposure=False, damping="fixed",
-                 marquardt_floor=0.0, robust=None):
+                 marquardt_floor=0.0, robust=None, depth_weight=None, invdepths=None, depth_masks=None):
         """ssim=False: the residual train_jvp.py uses (disable_ssim=True, [r; r]); ssim=True: the
         [r1; r2] residual with the SSIM term (batch_training_loss.py:18-30, gslm_ssim_*).
 
@@ -354,7 +398,26 @@ class LMProblem(_ProductOpts):
         loop, diagonal, cgls_jacobi, Marquardt damping, the batched problem and its union list -- runs unchanged;
         residuals[b] stay raw.  The plain residual on the LM rows only: ValueError with ssim, train_exposure or
         mask_xyz=False, and for anything that is not one of the three forms.  cgls_residual, which iterates on the raw
-        residuals, refuses a robust problem."""
+        residuals, refuses a robust problem.
+
+        depth_weight: None, or lambda_d >= 0 -- the inverse-depth residual.  A view with a target
+        (invdepths[b], or the camera's invdepthmap where depth_reliable is set; float32 [1, H, W]) and mask
+        (depth_masks[b], or the camera's depth_mask; None = every pixel) adds lambda_d sum (m_d (D - Dgt))^2 to the
+        loss, D the rendered inverse depth, and J_D^T W_d J_D, W_d = lambda_d m_d^2, to the products: its weights[b],
+        seeds[b] and residuals[b] are [4, H, W], the fourth plane gslm_lm_residual_depth's, and its rhs() and products
+        set GSLM_MV_DEPTH; the other views run the plain kernels.  On the LM rows 1/z is a constant, so J_D has columns
+        in scaling, rotation and opacity only, zero for a Gaussian without a head row: the active list, the lean loop
+        and the SH-rest projection apply unchanged.  depth_weight=0.0 is bitwise the problem without it.  The plain
+        residual with the fixed damping only: ValueError with ssim, train_exposure, robust, damping="marquardt",
+        set_damping_vector, diagonal (cgls_jacobi), cgls_residual, mask_xyz=False, the batched problem and the sharded
+        ones."""
+        self.depth_weight = depth_option(depth_weight)
+        if self.depth_weight is None and (invdepths is not None or depth_masks is not None):
+            raise ValueError("invdepths / depth_masks are the targets of depth_weight, which is None")
+        if self.depth_weight is not None and (ssim or train_exposure or robust is not None or not mask_xyz or
+                                              damping != "fixed"):
+            raise ValueError("depth_weight runs the [r; r] residual on the LM rows with the fixed damping "
+                             "(mask_xyz=True, no SSIM, no trained exposure, no robust loss, damping='fixed')")
         self.robust = robust_option(robust)
         if self.robust is not None and (ssim or train_exposure or not mask_xyz):
             raise ValueError("robust runs the [r; r] residual on the LM rows (mask_xyz=True, no SSIM, no trained "
@@ -401,6 +464,9 @@ class LMProblem(_ProductOpts):
         self.gts = [c.original_image.to(device) for c in cams] if gts is None else gts
         self.masks = [c.alpha_mask.to(device) for c in cams] if alpha_masks is None else alpha_masks
         self.views = [ViewRaster(_lib.view_from_camera(c, bg, model.active_sh_degree), device) for c in cams]
+        # per view (target, mask) of the depth residual, None for a view without one (and always without depth_weight)
+        self.depth = (depth_targets(cams, invdepths, depth_masks, device) if self.depth_weight is not None
+                      else [None] * len(cams))
         self.stream = _lib.stream_handle(device)
         # >= 3 x 1024 doubles: gslm_cg_update_monitor's three partial sums
         self.dot_scratch = torch.empty(max(lib.gslm_dot_scratch_bytes(max(P, self.layout.numel)) // 8, 3 * 1024) + 8,
@@ -443,11 +509,13 @@ class LMProblem(_ProductOpts):
         if self.train_exposure:
             self._exp_rhs.zero_()
         for b, vr in enumerate(self.views):
-            R = vr.forward(g, self.stream, want_invdepth=False)
-            if self.residuals[b] is None or self.residuals[b].shape != R.shape:
-                self.residuals[b] = torch.empty_like(R)
-                self.weights[b] = torch.empty_like(R)
-                self.seeds[b] = torch.empty_like(R)
+            dt = self.depth[b]
+            R = vr.forward(g, self.stream, want_invdepth=dt is not None)
+            planes = (4 if dt is not None else 3,) + tuple(R.shape[1:])  # (the fourth: the depth block's)
+            if self.residuals[b] is None or tuple(self.residuals[b].shape) != planes:
+                self.residuals[b] = R.new_empty(planes)
+                self.weights[b] = R.new_empty(planes)
+                self.seeds[b] = R.new_empty(planes)
                 if self.train_exposure:
                     self._exp_u[b] = torch.empty_like(R)
             m = self.masks[b]
@@ -493,6 +561,13 @@ class LMProblem(_ProductOpts):
                                        self.seeds[b].data_ptr(), self.res_scratch.data_ptr(),
                                        self.res_scratch.numel() * 8, loss.data_ptr(), int(b > 0), self.stream),
                   "gslm_lm_residual")
+            if dt is not None:  # planes 0-2 above; plane 3 and the loss's depth term (stream order: one scratch)
+                off = 12 * vr.H * vr.W
+                check(lib.gslm_lm_residual_depth(
+                    vr.H, vr.W, vr.invdepth.data_ptr(), dt[0].data_ptr(), None if dt[1] is None else dt[1].data_ptr(),
+                    self.depth_weight, self.residuals[b].data_ptr() + off, self.weights[b].data_ptr() + off,
+                    self.seeds[b].data_ptr() + off, self.res_scratch.data_ptr(), self.res_scratch.numel() * 8,
+                    loss.data_ptr(), 1, self.stream), "gslm_lm_residual_depth")
         self.loss = loss
         return loss
 
@@ -512,6 +587,7 @@ class LMProblem(_ProductOpts):
             ys = self.layout.grads_struct(out)
             for b, vr in enumerate(self.views):
                 opts = self._opts(vr, 2 | 4 | (STAGE_OVERWRITE if b == 0 else 0))  # RENDER | GATHER
+                opts.flags |= self._depth_flag(b)
                 opts.pixel_seed = self.seeds[b].data_ptr()
                 vr.product(g, ys, self.seeds[b].data_ptr(), 1, ys, opts, self.stream, "gslm_matvec_view_ex")
                 vr.tail_clean = True
@@ -528,6 +604,14 @@ class LMProblem(_ProductOpts):
             self.rhs_full(full)
             return self._mark_rhs(self.project(full, out), fused=False)
         return self._mark_rhs(self.rhs_full(out), fused=False)
+
+    def _depth_flag(self, b):
+        """GSLM_MV_DEPTH for a view with a depth term (its weights and seeds are [4, H, W]), else 0."""
+        return MV_DEPTH if self.depth[b] is not None else 0
+
+    def _no_depth(self, what):
+        if self.depth_weight is not None:
+            raise ValueError(f"{what} does not carry the depth residual (depth_weight)")
 
     def _mark_rhs(self, out, fused=True):
         """Remember the J^T b this problem produced (exposure slice zeroed): cgls_fused may then skip the exposure
@@ -558,9 +642,10 @@ class LMProblem(_ProductOpts):
         out.zero_()
         grads = self.full_layout.grads_struct(out, accumulate=True)
         for b, vr in enumerate(self.views):
-            dL = self.seeds[b]  # -2 m 1[0 <= R <= 1] r, from gslm_lm_residual
+            dL = self.seeds[b]  # -2 m 1[0 <= R <= 1] r, from gslm_lm_residual (plane 3: the depth block's seed)
+            dD = dL.data_ptr() + 12 * vr.H * vr.W if self.depth[b] is not None else None
             check(lib.gslm_backward(ctypes.byref(vr.view), ctypes.byref(g), vr.geom.data_ptr(), vr.binning.data_ptr(),
-                                    vr.N, vr.image.data_ptr(), dL.data_ptr(), None, vr.scratch.data_ptr(),
+                                    vr.N, vr.image.data_ptr(), dL.data_ptr(), dD, vr.scratch.data_ptr(),
                                     vr.scratch.numel(), ctypes.byref(grads), self.stream), "gslm_backward")
             vr.tail_clean = False
         self._apply_mask(out, self.full_layout)
@@ -666,6 +751,7 @@ class LMProblem(_ProductOpts):
             raise ValueError("a damping vector runs the plain product (no lean loop, SSIM or trained exposure)")
         for b, vr in enumerate(self.views):
             opts = self._opts(vr, STAGE_ALL | (STAGE_OVERWRITE if b == 0 else 0), cg_ctl)
+            opts.flags |= self._depth_flag(b)
             opts.damp7 = self._damps if (damp and b == 0 and dvec is None) else None
             if pre is not None and b == 0:
                 ss = self._pre_opts(opts, v, pre)  # noqa: F841  (kept alive for the call)
@@ -762,6 +848,7 @@ class LMProblem(_ProductOpts):
         GSLM_STAGE_SCREEN); pre as in matvec_dot (applied with the first view)."""
         if self.train_exposure:
             raise ValueError("the sharded exchanges do not carry trained exposure")
+        self._no_depth("the sharded exchange")
         g = raw_gaussians(self.model)
         vs = self.layout.grads_struct(v)
         ys = self.layout.grads_struct(v)  # unused by the SCREEN stage
@@ -831,6 +918,7 @@ class LMProblem(_ProductOpts):
         if d is None:
             self._dvec = None
             return
+        self._no_depth("set_damping_vector")
         if self.ssim or self.train_exposure or not self.mask_xyz or self.layout.rest_views or self._active is not None:
             raise ValueError("set_damping_vector: the [r; r] residual on the LM rows of LMProblem (mask_xyz=True, no "
                              "SSIM, no trained exposure, not the batched problem or an active view)")
@@ -858,6 +946,7 @@ class LMProblem(_ProductOpts):
         one copy of the [r; r] pair)."""
         if self.ssim or self.train_exposure:
             raise ValueError("jv_residual: the disable_ssim residual without trained exposure only")
+        self._no_depth("jv_residual (the residual-space recursion)")
         g = raw_gaussians(self.model)
         vs = self.layout.grads_struct(v)
         for b, vr in enumerate(self.views):
@@ -874,6 +963,7 @@ class LMProblem(_ProductOpts):
         groups zero.  Overwrites out."""
         if self.train_exposure:
             raise ValueError("jt_residual: the residual-space recursion does not carry trained exposure")
+        self._no_depth("jt_residual (the residual-space recursion)")
         g = raw_gaussians(self.model)
         ys = self.layout.grads_struct(out)
         for b, vr in enumerate(self.views):
@@ -981,6 +1071,7 @@ class LMProblem(_ProductOpts):
         map when it has one and builds it otherwise (the products after it then reuse it).  The plain residual on the
         LM rows only: ValueError with mask_xyz=False, ssim, train_exposure, or the batched problem's coordinates.
         With a damping vector (damping="marquardt", set_damping_vector) damp=True adds d: diag + d."""
+        self._no_depth("diagonal (cgls_jacobi, Marquardt damping)")
         if (not self.mask_xyz or self.ssim or self.train_exposure or self.layout.rest_views or
                 self._active is not None):
             raise ValueError("diagonal: the [r; r] residual on the LM rows (mask_xyz=True, no SSIM, no trained "
@@ -1032,7 +1123,9 @@ class BatchedLMProblem(LMProblem, _StageTimes):
 
     def __init__(self, model, cams, bg, gts=None, alpha_masks=None, mask_xyz=True, damp=None, device="cuda",
                  ssim=False, lambda_dssim=0.2, sh_projection=False, union_active=False, damping="fixed",
-                 marquardt_floor=0.0, robust=None):
+                 marquardt_floor=0.0, robust=None, depth_weight=None, invdepths=None, depth_masks=None):
+        if depth_weight is not None or invdepths is not None or depth_masks is not None:
+            raise ValueError("BatchedLMProblem does not carry the depth residual (depth_weight is LMProblem's)")
         if damping != "fixed" or marquardt_floor != 0.0:
             raise ValueError("BatchedLMProblem runs the fixed damping (damping='marquardt' is LMProblem's)")
         if not mask_xyz:
@@ -1790,7 +1883,8 @@ class LossEvaluator:
     same).  `reduce`: a callable summing it over the ranks that hold the other views (gslm.parallel.allreduce_loss)."""
 
     def __init__(self, model, cams, bg, device="cuda", batch=8, gts=None, alpha_masks=None, reduce=None, streams=3,
-                 device_count=False, train_exposure=False, fused_exposure=False, robust=None):
+                 device_count=False, train_exposure=False, fused_exposure=False, robust=None, depth_weight=None,
+                 invdepths=None, depth_masks=None):
         """train_exposure: the loss is taken on the exposed colour of each camera's row of model._exposure, as
         LMProblem(train_exposure=True) takes it: 2 sum ||m clamp01(C) - gt||^2.  evaluate() then renders each view
         with the full forward and runs gslm_lm_residual_exposure in its loss-only mode (no fused loss epilogue, no
@@ -1802,7 +1896,21 @@ class LossEvaluator:
         robust: None, ("huber", delta) or ("cauchy", delta), as LMProblem takes it: the loss is 2 sum rho(r^2), summed
         in the blends' epilogues (gslm_rasterize_loss_robust and its slot and sets forms) -- batches, side streams
         and GSLM_LOSS_SET_GROUP as ever.  ValueError with device_count=True or train_exposure (neither blend has a
-        robust form)."""
+        robust form).
+        depth_weight: None, or lambda_d >= 0 as LMProblem takes it, with the targets invdepths / depth_masks (default:
+        the cameras' invdepthmap where depth_reliable is set, and depth_mask): a view with a target adds lambda_d sum
+        (m_d (D - Dgt))^2, summed in the blend's epilogue (gslm_rasterize_loss_depth; evaluate_points through
+        gslm_rasterize_loss_slot_depth per set -- there is no all-sets form, so GSLM_LOSS_SET_GROUP above 1 falls back to
+        per set for those views); the other views run the plain blends.  ValueError with device_count=True,
+        train_exposure or robust."""
+        self.depth_weight = depth_option(depth_weight)
+        if self.depth_weight is None and (invdepths is not None or depth_masks is not None):
+            raise ValueError("invdepths / depth_masks are the targets of depth_weight, which is None")
+        if self.depth_weight is not None and (device_count or train_exposure or robust is not None):
+            raise ValueError("depth_weight: the device-count, exposure and robust blends have no depth form "
+                             "(device_count=False, train_exposure=False, robust=None)")
+        self.depth = (depth_targets(cams, invdepths, depth_masks, device) if self.depth_weight is not None
+                      else [None] * len(cams))
         self.robust = robust_option(robust)
         if self.robust is not None and (device_count or train_exposure):
             raise ValueError("robust: the device-count blend and the exposure blends have no robust form "
@@ -1917,7 +2025,14 @@ class LossEvaluator:
         pointer of the exposure rows, the blend then gslm_rasterize_loss_exposure with the camera's row; with `robust`
         gslm_rasterize_loss_robust."""
         mp = self._mask_ptr(i)
-        if self._robust is not None:
+        dt = self.depth[i]
+        if dt is not None:
+            check(lib.gslm_rasterize_loss_depth(ctypes.byref(vw), P, sl["geom"].data_ptr(), sl["binning"].data_ptr(),
+                                                sl["binning"].numel(), N, self.gts[i].data_ptr(), mp, dt[0].data_ptr(),
+                                                None if dt[1] is None else dt[1].data_ptr(), self.depth_weight,
+                                                scr.data_ptr(), scr.numel() * 8, out, 0, sh),
+                  "gslm_rasterize_loss_depth")
+        elif self._robust is not None:
             check(lib.gslm_rasterize_loss_robust(ctypes.byref(vw), P, sl["geom"].data_ptr(), sl["binning"].data_ptr(),
                                                  sl["binning"].numel(), N, self.gts[i].data_ptr(), mp,
                                                  ctypes.byref(self._robust), scr.data_ptr(), scr.numel() * 8, out, 0,
@@ -2169,7 +2284,8 @@ class LossEvaluator:
                                              binning.numel(), N, ge, n, sb, sh), "gslm_union_binning")
                 mp = self._mask_ptr(i)
                 xoff = 48 * self.exp_idx[i] if xs is not None else 0
-                if self.loss_sets > 1:  # groups of loss_sets sets, one pass over the union list each
+                dt = self.depth[i]
+                if self.loss_sets > 1 and dt is None:  # groups of loss_sets sets, one pass over the union list each
                     gsz = min(self.loss_sets, n)
                     scr = self._sets_scratch(k, gsz, H, W)
                     for a0 in range(0, n, gsz):
@@ -2196,6 +2312,13 @@ class LossEvaluator:
                     continue
                 scr = self.loss_scratch[k % len(self.streams)]
                 for a in range(n):
+                    if dt is not None:  # (no all-sets form with depth: per set whatever loss_sets says)
+                        check(lib.gslm_rasterize_loss_slot_depth(
+                            ctypes.byref(vw), P, sl["geoms"][a].data_ptr(), sb, binning.data_ptr(), binning.numel(), N,
+                            a, n, self.gts[i].data_ptr(), mp, dt[0].data_ptr(),
+                            None if dt[1] is None else dt[1].data_ptr(), self.depth_weight, scr.data_ptr(),
+                            scr.numel() * 8, losses[a].data_ptr() + 8 * i, 0, sh), "gslm_rasterize_loss_slot_depth")
+                        continue
                     if xs is not None:
                         check(lib.gslm_rasterize_loss_slot_exposure(
                             ctypes.byref(vw), P, sl["geoms"][a].data_ptr(), sb, binning.data_ptr(), binning.numel(), N,
@@ -2269,7 +2392,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
             verbose=False, device="cuda", sh_projection="auto", recursion="fused", exchange="auto", group=None,
             val_batch=8, timing=False, backend=None, line_search="union", val_at_start=False, cache_val=True,
             multiview="loop", union_active=False, train_exposure=False, val_exposure="forward", precond=None,
-            damping="fixed", marquardt_floor=0.0, robust=None):
+            damping="fixed", marquardt_floor=0.0, robust=None, depth_weight=None):
     """One LM step of train_jvp.py:237-289: loss, CGLS on the normal equations, backtracking line search.
 
     Single process: LMProblem over `cams` (with one training view the SH-rest group of the CG vectors is carried
@@ -2320,6 +2443,13 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     robust loss on the validation views (LossEvaluator(robust=...)).  With either multiview, union_active, either
     precond, either damping and either line_search; ValueError for anything else than the three forms, and for a
     sharded run, a backend, recursion="cgls", train_exposure=True or mask_xyz=False.  The result reports `robust`.
+    depth_weight: None (today's step, launch for launch) or lambda_d >= 0: the step also minimises the inverse-depth
+    residual lambda_d sum (m_d (D - Dgt))^2 of every training camera that carries a target (invdepthmap with
+    depth_reliable set, and depth_mask; LMProblem(depth_weight=...)), and the line search takes the combined loss on
+    the validation cameras (LossEvaluator(depth_weight=...)).  The single-process step with multiview="loop",
+    recursion="fused", mask_xyz=True, precond=None and damping="fixed", without trained exposure, a robust loss or a
+    backend -- anything else, or a weight that is negative or not finite, raises ValueError.  The result reports
+    `depth_weight`.
     backend: (problem_cls, evaluator_cls, solver) replacing (LMProblem, LossEvaluator, cgls_fused) -- the CPU
     multi-process tests run this same driver, sharding and reductions on the oracle restatement."""
     import time
@@ -2368,7 +2498,16 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
                                not mask_xyz):
         raise ValueError("robust is the single-process step with recursion='fused', mask_xyz=True, no trained "
                          "exposure and no backend")
+    depth_weight = depth_option(depth_weight)
+    if depth_weight is not None and (sharded or backend is not None or recursion != "fused" or train_exposure or
+                                     not mask_xyz or robust is not None or precond is not None or
+                                     damping != "fixed" or (multiview == "batched" and len(cams) > 1)):
+        raise ValueError("depth_weight is the single-process step with multiview='loop', recursion='fused', "
+                         "mask_xyz=True, precond=None and damping='fixed': no trained exposure, robust loss or "
+                         "backend")
     rob_kw = {"robust": robust} if robust is not None else {}
+    if depth_weight is not None:
+        rob_kw["depth_weight"] = depth_weight  # (the problem and the evaluator take it as they take `robust`)
     exp_kw = {"train_exposure": True} if train_exposure else {}
     damp_kw = {"damping": "marquardt", "marquardt_floor": marquardt_floor} if damping == "marquardt" else {}
     fused_exposure = val_exposure == "fused"
@@ -2421,6 +2560,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     imgs = [(getattr(c, "original_image", None), getattr(c, "alpha_mask", None)) for c in mine_val]
     vkey = (id(model), model.active_sh_degree, tuple(id(c) for c in mine_val), tuple(id(t) for p in imgs for t in p),
             str(device), val_batch, evaluator_cls, sharded, id(group), bool(train_exposure), val_exposure, robust,
+            depth_weight, tuple(id(getattr(c, k, None)) for c in mine_val for k in ("invdepthmap", "depth_mask")),
             tuple(float(x) for x in torch.as_tensor(bg).reshape(-1).tolist()))
     hit = _VAL_CACHE.get("last") if cache_val else None
     if hit is not None and hit[0] == vkey:
@@ -2484,6 +2624,8 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
         out["damping"] = damping
     if robust is not None:
         out["robust"] = robust
+    if depth_weight is not None:
+        out["depth_weight"] = depth_weight
     if val_at_start:
         out["val_start_loss"] = val_start
     if union and getattr(val, "union_counts", None):

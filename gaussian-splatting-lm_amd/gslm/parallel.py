@@ -224,6 +224,8 @@ def ShardedLMProblem(model, cams, bg, group=None, all_cams=None, exchange="auto"
     ShardedOperator's own choice."""
     if problem_cls is None:
         from gslm.lm import LMProblem as problem_cls
+    if any(kw.get(k) is not None for k in ("depth_weight", "invdepths", "depth_masks")):
+        raise ValueError("the sharded problems do not carry the depth residual (depth_weight is LMProblem's)")
     rank, n = world()
     if n > 1 or (all_cams is not None and len(all_cams) > 1) or exchange == "gaussian":
         # the SH-rest span is one view's: the global batch has several (and the Gaussian-sharded exchange

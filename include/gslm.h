@@ -847,6 +847,60 @@ int gslm_lm_residual_robust(int32_t H, int32_t W, const float* color, const floa
                             const gslm_robust* robust, float* residual, float* weight, float* seed, void* scratch,
                             size_t scratch_bytes, double* loss_dev, int32_t accumulate, void* stream);
 
+/* ---- The inverse-depth residual of the LM step (still ABI 9, additive) ----
+ * The reference's solver state reserves a third residual block, Ll1depth_per_pixel (solver/loss_image_state.py), for
+ * the cameras' invdepthmap / depth_mask; here it is a least-squares block that enters the loss once:
+ *   loss = 2 sum ||m clamp01(R) - gt||^2 + lambda_d sum (m_d (D - Dgt))^2,
+ *   A v  = sum_b (2 J_c^T W_c J_c + J_D^T W_d J_D) v + D v,   W_d = lambda_d m_d^2,
+ *   J^T b = (the colour part) - sum_b J_D^T (lambda_d m_d^2 (D - Dgt)),
+ * D the rendered inverse depth (gslm_rasterize's out_invdepth: no background term, no clamp).  On the LM rows
+ * (xyz frozen) a Gaussian's 1/z is a constant, so J_D has columns through alpha only -- scaling, rotation, opacity --
+ * and the LM row format, the row map, the active list and the SH-rest projection are unchanged.
+ *
+ * gslm_lm_residual_depth: the block's epilogue for one view.  invdepth / invdepth_gt / residual / weight / seed are
+ * [H,W] planes; depth_mask [H,W] or NULL (= 1).  Per pixel, in float, in this order and uncontracted:
+ *   r        = m * (invdepth - invdepth_gt)
+ *   weight   = (float)depth_weight * (m * m)       (plane 3 of a GSLM_MV_DEPTH pixel_weight)
+ *   seed     = (-weight) * r                       (plane 3 of a GSLM_MV_DEPTH pixel_seed; for a mask of zeros and
+ *                                                   ones this is -lambda_d m_d^2 (D - Dgt), the term of J^T b above)
+ * and *loss_dev = [*loss_dev if accumulate] + sum over pixels of depth_weight * ((double)r * (double)r): per thread in
+ * pixel order p, p + stride, ..., then gslm_lm_residual's block sums and final pass, without its factor 2.
+ * residual, weight and seed are optional (NULL: not written; all three NULL: the loss alone).  A NaN invdepth gives a
+ * NaN r, seed and loss.  scratch >= gslm_residual_scratch_bytes(H, W).  GSLM_ERR_INVALID, before any launch and with
+ * the outputs untouched: negative sizes, a NULL invdepth / invdepth_gt with H W > 0, a NULL loss_dev or scratch, a
+ * depth_weight that is negative or not finite; GSLM_ERR_CAPACITY for a scratch that is too small. */
+int gslm_lm_residual_depth(int32_t H, int32_t W, const float* invdepth, const float* invdepth_gt,
+                           const float* depth_mask, double depth_weight, float* residual, float* weight, float* seed,
+                           void* scratch, size_t scratch_bytes, double* loss_dev, int32_t accumulate, void* stream);
+/* GSLM_MV_DEPTH in opts->flags (no extension struct: it composes with GSLM_MV_LEAN and GSLM_MV_SH_REST_PROJECTED):
+ * pixel_weight is [4,H,W] and opts->pixel_seed, when given, is [4,H,W]; the fourth plane is the depth block's weight
+ * or seed (gslm_lm_residual_depth's).  It selects the RENDER stage's kernel only: the tile pass carries
+ * dD = sum 1/z d(alpha T) beside the colour tangent, u_3 = w_3 dD seeds the back-to-front pass, and dL/dalpha gains
+ * <1/z, u_3>; with a fourth plane of zeros y, dot_vy and J^T b are bitwise those of the call without the flag.
+ * Accepted by gslm_matvec_view_ex and gslm_matvec_view_active.  GSLM_ERR_INVALID before anything is launched (outputs
+ * untouched): mask_xyz = 0, GSLM_MV_EXPOSURE, GSLM_MV_DAMP_VEC, jv_out, GSLM_STAGE_SCREEN; and from gslm_tangent_views,
+ * gslm_gather_views and gslm_gather_screen (and their _active forms). */
+#define GSLM_MV_DEPTH 32
+/* The line search's loss with the depth block: gslm_rasterize_loss and gslm_rasterize_loss_slot (the same arguments,
+ * workspaces, scratch and error returns) with the inverse depth accumulated in the blend exactly as gslm_rasterize
+ * does and, per pixel after its three colour terms, the term depth_weight / 2 * ((double) r (double) r) of
+ * r = m_d (D - invdepth_gt) (gslm_lm_residual_depth's float arithmetic), which the final pass doubles with the tile
+ * sums: *loss_dev = [*loss_dev if accumulate] + 2 sum ||m clamp01(R) - gt||^2 + depth_weight sum r^2, the loss of
+ * gslm_rasterize + gslm_lm_residual + gslm_lm_residual_depth up to the grouping of the double sum.  invdepth_gt [H,W];
+ * depth_mask [H,W] or NULL (= 1).  The slot form blends set `slot` of a union binning by that set's own masks and
+ * records (which carry 1/z), as gslm_rasterize_loss_slot does.  GSLM_ERR_INVALID before any launch, the loss
+ * untouched: a NULL invdepth_gt, a depth_weight that is negative or not finite, and everything the plain forms
+ * refuse.  There is no all-sets, device-count, exposure or robust form. */
+int gslm_rasterize_loss_depth(const gslm_view* view, int64_t P, void* geom, void* binning, size_t binning_bytes,
+                              int64_t num_rendered, const float* gt, const float* alpha_mask, const float* invdepth_gt,
+                              const float* depth_mask, double depth_weight, void* scratch, size_t scratch_bytes,
+                              double* loss_dev, int32_t accumulate, void* stream);
+int gslm_rasterize_loss_slot_depth(const gslm_view* view, int64_t P, const void* geom, size_t set_bytes,
+                                   const void* binning, size_t binning_bytes, int64_t num_rendered, int32_t slot,
+                                   int32_t n_sets, const float* gt, const float* alpha_mask, const float* invdepth_gt,
+                                   const float* depth_mask, double depth_weight, void* scratch, size_t scratch_bytes,
+                                   double* loss_dev, int32_t accumulate, void* stream);
+
 /* ---- SSIM residual of the LM step (solver/batch_training_loss.py:18-30 with
  * disable_ssim=False, FUSED_SSIM_AVAILABLE=False, on utils/loss_utils.py:91-122 ssim_per_pixel) ----
  * Per view: r1 = a sqrt(|x - gt| + 1e-6), r2 = b sqrt(|1 - SSIM(x, gt)| + 1e-6) with x = m clamp(color, 0, 1),
