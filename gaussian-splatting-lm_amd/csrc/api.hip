@@ -906,6 +906,8 @@ enum : uint32_t {
   F_UNMASKED = 1u << 20,    // mask_xyz = 0
   F_TAIL_DIRTY = 1u << 21,  // no GSLM_MV_TAIL_CLEAN
   F_DEPTH = 1u << 22,       // GSLM_MV_DEPTH
+  F_XYZ = 1u << 23,         // GSLM_MV_XYZ
+  F_LIST = 1u << 24,        // the union-list form of an entry point (gslm_gather_views_active, gslm_tangent_views_active)
 };
 // Which go together, once: a call in `mode` with any of `excludes` is refused (GSLM_ERR_INVALID).
 static const struct { uint32_t mode, excludes; const char* msg; } kExcludes[] = {
@@ -929,6 +931,10 @@ static const struct { uint32_t mode, excludes; const char* msg; } kExcludes[] = 
     {F_DEPTH, F_UNMASKED | F_EXPOSURE | F_DAMP_VEC | F_JV_OUT | F_SCREEN | E_GATHER | E_TANGENT_VIEWS,
      "GSLM_MV_DEPTH is an option of gslm_matvec_view_ex / gslm_matvec_view_active on the LM rows (mask_xyz); it "
      "excludes GSLM_MV_EXPOSURE, GSLM_MV_DAMP_VEC, jv_out and the SCREEN stage"},
+    {F_XYZ, E_MATVEC | E_GATHER_SCREEN | E_TANGENT_VIEWS | F_LIST | F_DAMP_VEC | F_DEPTH | F_EXPOSURE,
+     "GSLM_MV_XYZ is an option of gslm_gather_views (the matvec entry points have mask_xyz; the list forms, "
+     "gslm_gather_screen and gslm_tangent_views run without it); it excludes GSLM_MV_DAMP_VEC, GSLM_MV_DEPTH and "
+     "GSLM_MV_EXPOSURE"},
 };
 static bool excluded(uint32_t f, uint32_t mode) {
   for (const auto& r : kExcludes)
@@ -968,7 +974,7 @@ static void plan_base(uint32_t entry, uint32_t accepts, const gslm_matvec_opts* 
                (st & GSLM_STAGE_GATHER ? F_GATHER : 0) | (st & GSLM_STAGE_SCREEN ? F_SCREEN : 0) |
                (st & GSLM_STAGE_OVERWRITE ? F_OVERWRITE : 0) | (fl & GSLM_MV_LEAN ? F_LEAN : 0) |
                (fl & GSLM_MV_EXPOSURE ? F_EXPOSURE : 0) | (fl & GSLM_MV_DAMP_VEC ? F_DAMP_VEC : 0) |
-               (fl & GSLM_MV_DEPTH ? F_DEPTH : 0) |
+               (fl & GSLM_MV_DEPTH ? F_DEPTH : 0) | (fl & GSLM_MV_XYZ ? F_XYZ : 0) |
                ((fl & GSLM_MV_SH_REST_PROJECTED) && M > 1 ? F_PROJECTED : 0) | (fl & GSLM_MV_TAIL_CLEAN ? 0 : F_TAIL_DIRTY) |
                (mask_xyz ? 0 : F_UNMASKED);
   if (o) f |= (o->pixel_seed ? F_SEED : 0) | (o->jv_out ? F_JV_OUT : 0) | (o->trec_in ? F_TREC_IN : 0) |
@@ -1030,6 +1036,10 @@ static int make_flatk(const GaussK& g, const GradK& y, const GradK& vin, const d
 
 // The GATHER stage's FlatK from the plan's damp7, OVERWRITE, partials, projection and SH-rest coordinates.
 static int plan_flat(const GaussK& g, const gslm_grads* y, const gslm_grads* vin, Plan* pl) {
+  if ((pl->f & F_XYZ) && (!y->means3D || !vin->means3D)) {
+    set_error("gather_views: GSLM_MV_XYZ needs the xyz groups of v and y");
+    return GSLM_ERR_INVALID;
+  }
   return make_flatk(g, make_gradk(y), make_gradk(vin), pl->damp7, (pl->f & F_OVERWRITE) != 0, pl->part, &pl->flat,
                     (pl->f & F_PROJECTED) != 0, pl->rc.R ? pl->rc.V : 0);
 }
@@ -1045,7 +1055,8 @@ static int plan_matvec(uint32_t entry, const gslm_matvec_opts* opts, const Bound
   const uint32_t f = pl->f;
   int st;
   // (one extension struct lies behind the base: a flag's exclusions are checked before its extension is read)
-  if (excluded(f, F_DEPTH) || excluded(f, F_DAMP_VEC) || excluded(f, E_MATVEC_EX) || excluded(f, F_EXPOSURE))
+  if (excluded(f, F_XYZ) || excluded(f, F_DEPTH) || excluded(f, F_DAMP_VEC) || excluded(f, E_MATVEC_EX) ||
+      excluded(f, F_EXPOSURE))
     return GSLM_ERR_INVALID;
   // GSLM_MV_EXPOSURE: opts is the base of a gslm_matvec_opts_exposure; RENDER runs the product under the camera's
   // trained exposure and sums the 12 exposure rows
@@ -1546,8 +1557,8 @@ int gslm_gather_screen(const gslm_view* views, int32_t nviews, const gslm_gaussi
     return GSLM_ERR_INVALID;
   }
   Plan pl;
-  plan_base(E_GATHER_SCREEN, F_DAMP_VEC | F_DAMP7 | F_REST_BASIS | F_DEPTH, opts, true, 0, &pl);
-  if (excluded(pl.f, E_GATHER) || excluded(pl.f, F_DEPTH)) return GSLM_ERR_INVALID;
+  plan_base(E_GATHER_SCREEN, F_DAMP_VEC | F_DAMP7 | F_REST_BASIS | F_DEPTH | F_XYZ, opts, true, 0, &pl);
+  if (excluded(pl.f, F_XYZ) || excluded(pl.f, E_GATHER) || excluded(pl.f, F_DEPTH)) return GSLM_ERR_INVALID;
   ViewK vk[16];
   GaussK g;
   int st;
@@ -1574,8 +1585,10 @@ static int gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t 
     return GSLM_ERR_INVALID;
   }
   Plan pl;
-  plan_base(E_GATHER_VIEWS, F_DAMP_VEC | F_DAMP7 | F_REST_BASIS | F_DEPTH, opts, true, 0, &pl);
-  if (excluded(pl.f, E_GATHER) || excluded(pl.f, F_DEPTH)) return GSLM_ERR_INVALID;
+  // (GSLM_MV_EXPOSURE is decoded for GSLM_MV_XYZ's refusal alone: without that flag it is ignored as ever)
+  plan_base(E_GATHER_VIEWS | (active ? F_LIST : 0), F_DAMP_VEC | F_DAMP7 | F_REST_BASIS | F_DEPTH | F_XYZ | F_EXPOSURE,
+            opts, true, 0, &pl);
+  if (excluded(pl.f, F_XYZ) || excluded(pl.f, E_GATHER) || excluded(pl.f, F_DEPTH)) return GSLM_ERR_INVALID;
   if (active && (na > gi->P || !hrow || hstride < na + 1 || fstride < na || (na > 0 && (!ids || !aflags)))) {
     set_error("gather_views_active: n_active above P, a NULL list or a stride that does not hold it");
     return GSLM_ERR_INVALID;
@@ -1607,7 +1620,7 @@ static int gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t 
   if (pl.rows > 0 && (st = plan_flat(g, y, vin, &pl))) return st;
   pl.flat.dot_part = pl.part;  // (an empty call still finishes its dot: the sum of no partials)
   return launch_gather_views(vk, gbs, sbs, nr, nviews, g, pl.flat, pl.dot_out, (hipStream_t)stream, pl.rc, ids,
-                             active ? na : -1, hrow, hstride, aflags, fstride);
+                             active ? na : -1, hrow, hstride, aflags, fstride, (pl.f & F_XYZ) != 0);
 }
 
 int gslm_gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t nviews, const gslm_gaussians* gi,
@@ -1647,8 +1660,8 @@ static int tangent_views(const gslm_view* views, int32_t nviews, const gslm_gaus
     return GSLM_ERR_INVALID;
   }
   Plan pl;
-  plan_base(E_TANGENT_VIEWS, F_XPBY | F_REST_BASIS | F_DEPTH, opts, mask_xyz != 0, 0, &pl);
-  if (excluded(pl.f, F_DEPTH)) return GSLM_ERR_INVALID;
+  plan_base(E_TANGENT_VIEWS | (active ? F_LIST : 0), F_XPBY | F_REST_BASIS | F_DEPTH | F_XYZ, opts, mask_xyz != 0, 0, &pl);
+  if (excluded(pl.f, F_XYZ) || excluded(pl.f, F_DEPTH)) return GSLM_ERR_INVALID;
   ViewK vk[MAX_SCREEN_VIEWS];
   GaussK g;
   int st;

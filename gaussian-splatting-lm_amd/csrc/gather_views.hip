@@ -5,6 +5,8 @@
 //   y = [y +] [D v +] sum_b C_b^T (sum of Gaussian i's head rows in view b),   <v, y> partials
 // Same row sums (block_sum_rows<2> over the same 256-Gaussian partition), same chain and the same accumulation
 // order as k_rowsum_screen x V + k_gather_screen, so the results are those kernels' bit for bit.
+// XYZ (GSLM_MV_XYZ): the views' head rows are the 48-byte ones of an unmasked RENDER stage (block_sum_rows<3>), the
+// chain includes the means (with the SH colour's view-direction term) and y's xyz group is written with the others.
 #include <type_traits>
 #include "gslm_gather.hpp"
 
@@ -44,12 +46,20 @@ __device__ __forceinline__ int64_t nrows_of(const WS& ws, const GaussK& g) {
 // j of v, y, hrow and aflags.  A block's 256 consecutive listed Gaussians still own one contiguous range of head rows
 // in every view -- the Gaussians between two listed ones own none in any view -- so the row sums and their order are
 // the full kernel's (k_gather_lm<..., ACTIVE> for one view); the view's tiles, goff, hscan and clampw are not read.
-template <bool COORDS, bool ACTIVE = false>
+template <bool COORDS, bool ACTIVE = false, bool XYZ = false>
 __global__ __launch_bounds__(256) void k_gather_views(ViewsK vs, std::conditional_t<ACTIVE, ActiveWsK, ViewWsK> ws,
                                                        GaussK g, FlatK o, RestK rc) {
+  static_assert(!(ACTIVE && XYZ), "k_gather_views: the union list's rows are the masked ones");
+  constexpr int ROWF4 = XYZ ? 3 : 2;  // float4 per head row
   extern __shared__ __attribute__((aligned(16))) float s_rest[];  // the views' row chunks, then the epilogue's stage
   __shared__ double s_dot[4];
   if (cg_stopped(vs.v[0])) return;  // a stopped solve (gslm_matvec_opts.cg_ctl): block-uniform, before any barrier
+  if constexpr (XYZ) {
+    // raw leaves with SH colours (make_flatk has refused anything else): as compile-time facts they drop the
+    // chain's other branches, which with the means' terms would not fit the scalar registers
+    g.cov3D = nullptr;
+    g.colors = nullptr;
+  }
   const int64_t nrows = nrows_of<ACTIVE>(ws, g);  // rows of v and y
   const int64_t i0 = (int64_t)blockIdx.x * blockDim.x;
   const int64_t j = i0 + threadIdx.x;
@@ -91,13 +101,17 @@ __global__ __launch_bounds__(256) void k_gather_views(ViewsK vs, std::conditiona
       const uint32_t n = i < g.P ? tiles[i] : 0u;
       const uint32_t R0 = hscan[goff[i0]], R1 = hscan[goff[il] + tiles[il]];
       const uint32_t h0 = i < g.P ? hscan[goff[i]] : R1, h1 = i < g.P ? hscan[goff[i] + n] : R1;
-      block_sum_rows<2>(rows, R0, R1, h0, h1 - h0, reinterpret_cast<float4*>(s_rest), G2);
+      block_sum_rows<ROWF4>(rows, R0, R1, h0, h1 - h0, reinterpret_cast<float4*>(s_rest), G2);
       if (!n) continue;
       clamp = (tiles + ws.clamp_off)[i] & 7u;
     }
     ChainOut co;
-    chain_vjp<true>(vs.v[b], g, i, true, clamp, G2, false, co);
+    chain_vjp<true>(vs.v[b], g, i, true, clamp, G2, /*want_means=*/XYZ, co);
     acc.dop += co.dop;
+    if constexpr (XYZ) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) acc.dmean[k] += co.dmean[k];
+    }
 #pragma unroll
     for (int k = 0; k < 3; ++k) acc.dscale[k] += co.dscale[k];
 #pragma unroll
@@ -125,7 +139,7 @@ __global__ __launch_bounds__(256) void k_gather_views(ViewsK vs, std::conditiona
     }
   }
   if constexpr (ACTIVE) g.P = ws.na;  // the epilogue writes rows j < na of y (it reads P and M of g only)
-  lm_epilogue<false>(g.M, g, acc, o, s_rest, s_dot);
+  lm_epilogue<XYZ>(g.M, g, acc, o, s_rest, s_dot);
 }
 
 // <v, y> from the blocks' partials: k_dot_final's sum (cg.hip), except that a stopped solve -- whose gather wrote no
@@ -146,7 +160,7 @@ __global__ __launch_bounds__(256) void k_dot_final_views(const double* __restric
 int launch_gather_views(const ViewK* views, const GeomBufs* gbs, const ScratchBufs* sbs, const int64_t* nr,
                         int nviews, const GaussK& g, const FlatK& o, double* dot_out, hipStream_t s, const RestK& rc,
                         const int32_t* ids, int64_t na, const uint32_t* hrow, int64_t hstride, const uint32_t* aflags,
-                        int64_t fstride) {
+                        int64_t fstride, bool xyz) {
   double* const dot_part = o.dot_part;
   const bool active = na >= 0;
   const int64_t nrows = active ? na : g.P;  // rows of v and y
@@ -165,6 +179,10 @@ int launch_gather_views(const ViewK* views, const GeomBufs* gbs, const ScratchBu
   }
   if (active && (!ids || !hrow || !aflags || hstride < na + 1 || fstride < na)) {
     set_error("internal: the active-list gather needs the union list and strides that hold it");
+    return GSLM_ERR_INVALID;
+  }
+  if (active && xyz) {
+    set_error("internal: the active-list gather runs on the LM rows (no GSLM_MV_XYZ)");
     return GSLM_ERR_INVALID;
   }
   ViewsK vs;
@@ -195,10 +213,14 @@ int launch_gather_views(const ViewK* views, const GeomBufs* gbs, const ScratchBu
   aw.hstride = hstride;
   aw.fstride = fstride;
   const unsigned nb = (unsigned)((nrows + 255) / 256);
-  const size_t chunk_lds = (size_t)GATHER_CHUNK * 2 * sizeof(float4);
+  const size_t chunk_lds = (size_t)GATHER_CHUNK * (xyz ? 3 : 2) * sizeof(float4);
   const size_t stage = (o.rest_V ? (size_t)256 * 3 * o.rest_V : sh_stage_floats<false>(g.M)) * sizeof(float);
   const size_t lds = (stage > chunk_lds ? stage : chunk_lds) + 16;
-  if (o.rest_V && active)
+  if (o.rest_V && xyz)
+    hipLaunchKernelGGL((k_gather_views<true, false, true>), dim3(nb), dim3(256), lds, s, vs, ws, g, o, rc);
+  else if (xyz)
+    hipLaunchKernelGGL((k_gather_views<false, false, true>), dim3(nb), dim3(256), lds, s, vs, ws, g, o, rc);
+  else if (o.rest_V && active)
     hipLaunchKernelGGL((k_gather_views<true, true>), dim3(nb), dim3(256), lds, s, vs, aw, g, o, rc);
   else if (o.rest_V)
     hipLaunchKernelGGL(k_gather_views<true>, dim3(nb), dim3(256), lds, s, vs, ws, g, o, rc);

@@ -685,12 +685,13 @@ int launch_gather_screen(const ViewK* views, int nviews, const GaussK& g, const 
                          const FlatK& o, hipStream_t s, const RestK& rc = RestK{});
 // every view's head rows (the LM row maps of gbs / sbs; nr[b] <= 0: view b rendered nothing, its buffers are not read)
 // summed and chained per Gaussian in one pass (gslm_gather_views, gather_views.hip); dot_out (or NULL) = the sum of
-// the dot_part partials, left alone by a stopped solve
+// the dot_part partials, left alone by a stopped solve.  xyz (GSLM_MV_XYZ): the head rows are an unmasked RENDER
+// stage's 48-byte ones and y's xyz group is written; not with a list
 int launch_gather_views(const ViewK* views, const GeomBufs* gbs, const ScratchBufs* sbs, const int64_t* nr,
                         int nviews, const GaussK& g, const FlatK& o, double* dot_out, hipStream_t s,
                         const RestK& rc = RestK{}, const int32_t* ids = nullptr, int64_t na = -1,
                         const uint32_t* hrow = nullptr, int64_t hstride = 0, const uint32_t* aflags = nullptr,
-                        int64_t fstride = 0);
+                        int64_t fstride = 0, bool xyz = false);
 // the union list of a view batch (gslm_active_union): nr[b] == 0 marks a view without a row map; flags [P] doubles as
 // the scan's output, scan_tmp: scan_tmp_bytes(P), total: one word; hrow [V][P + 1], aflags [V][P]
 int launch_active_union(const GeomBufs* gbs, const ScratchBufs* sbs, const int64_t* nr, int nviews, int64_t P,

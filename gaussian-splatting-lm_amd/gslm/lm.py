@@ -35,6 +35,7 @@ MV_LEAN = 4  # GSLM_MV_LEAN
 MV_EXPOSURE = 8  # GSLM_MV_EXPOSURE
 MV_DAMP_VEC = 16  # GSLM_MV_DAMP_VEC
 MV_DEPTH = 32  # GSLM_MV_DEPTH
+MV_XYZ = 64  # GSLM_MV_XYZ (gslm_gather_views)
 DIAG_TAIL_CLEAN = 1  # gslm_lm_diag_view flags: GSLM_DIAG_TAIL_CLEAN
 DIAG_ACCUMULATE = 2  # GSLM_DIAG_ACCUMULATE
 DIAG_SH_REST_PROJECTED = 4  # GSLM_DIAG_SH_REST_PROJECTED
@@ -599,7 +600,7 @@ class LMProblem(_ProductOpts):
             else:
                 out[e0:e1].zero_()
             return self._mark_rhs(out)
-        if self.layout.rest_projected:
+        if self.layout.rest_projected or self.layout.rest_views:
             full = torch.zeros(self.full_layout.numel, dtype=torch.float32, device=self.device)
             self.rhs_full(full)
             return self._mark_rhs(self.project(full, out), fused=False)
@@ -1116,7 +1117,16 @@ class BatchedLMProblem(LMProblem, _StageTimes):
     With V <= GSLM_MAX_REST_VIEWS views (and 3 V < 3 (K - 1)) the SH-rest group of every vector is carried in the 3 V
     gslm_rest_basis coordinates of the views' span (GSLM_SHARD_REST=full keeps the reference's layout); `expand` /
     `project` convert to and from `full_layout`.  The forwards, residuals and the loss are LMProblem's own.
-    mask_xyz=True and the disable_ssim residual only."""
+    mask_xyz=True and the disable_ssim residual only; BatchedXyzLMProblem is the batch with the positions free.
+
+    With the positions free (BatchedXyzLMProblem, mask_xyz=False) the tangent records are [V][P][12],
+    each view's RENDER stage runs unmasked into 48-byte head rows and the gather sets GSLM_MV_XYZ: the chain includes the means and
+    y's xyz group is written with the others.  J is evaluated at the current theta, so the SH-rest coordinates stay
+    valid.  rhs() is LMProblem's unmasked route (gslm_backward, then `project`), which drops the views' row maps: the
+    first product rebuilds them.  ValueError with union_active=True (the list's kernels are masked forms) and, as on
+    LMProblem, with robust."""
+
+    XYZ_FREE = False  # (BatchedXyzLMProblem: True)
 
     CHUNK = 16  # views per gslm_tangent_views / gslm_gather_views call
     STAGES = ("tangent_views", "tile_passes", "gather_views")  # (_StageTimes.stage_times)
@@ -1128,16 +1138,20 @@ class BatchedLMProblem(LMProblem, _StageTimes):
             raise ValueError("BatchedLMProblem does not carry the depth residual (depth_weight is LMProblem's)")
         if damping != "fixed" or marquardt_floor != 0.0:
             raise ValueError("BatchedLMProblem runs the fixed damping (damping='marquardt' is LMProblem's)")
-        if not mask_xyz:
-            raise ValueError("BatchedLMProblem runs on the LM rows (mask_xyz=True, train_jvp.py:221-227)")
+        if bool(mask_xyz) == self.XYZ_FREE:
+            raise ValueError("BatchedLMProblem runs on the LM rows (mask_xyz=True, train_jvp.py:221-227) and "
+                             "BatchedXyzLMProblem with the positions free (mask_xyz=False)")
+        if not mask_xyz and union_active:
+            raise ValueError("BatchedXyzLMProblem runs on all P Gaussians: union_active=True needs mask_xyz=True "
+                             "(gslm_tangent_views_active / gslm_gather_views_active are masked forms)")
         if ssim:
             raise ValueError("BatchedLMProblem runs the disable_ssim residual")
         if len(cams) < 1:
             raise ValueError("BatchedLMProblem needs at least one view")
         if sh_projection not in (False, None, "auto"):
             raise ValueError("sh_projection is LMProblem's single-view mode; the batch carries SH-rest coordinates")
-        super().__init__(model, cams, bg, gts=gts, alpha_masks=alpha_masks, mask_xyz=True, damp=damp, device=device,
-                         ssim=False, lambda_dssim=lambda_dssim, sh_projection=False, robust=robust)
+        super().__init__(model, cams, bg, gts=gts, alpha_masks=alpha_masks, mask_xyz=mask_xyz, damp=damp,
+                         device=device, ssim=False, lambda_dssim=lambda_dssim, sh_projection=False, robust=robust)
         full = self.full_layout
         P, K, V = full.P, full.K, len(cams)
         self.rest_views = V if (K > 1 and V <= _lib.GSLM_MAX_REST_VIEWS and 3 * V < 3 * (K - 1)
@@ -1148,7 +1162,8 @@ class BatchedLMProblem(LMProblem, _StageTimes):
         self._views_arr = (_lib.GslmView * V)(*[vr.view for vr in self.views])
         # allocated once: every view's visibility words and tangent records, the SH-rest factors
         self._flags = torch.zeros(V, max(P, 1), dtype=torch.int32, device=device)
-        self._trec = torch.zeros(V, max(P, 1), 8, dtype=torch.float32, device=device)
+        self._trec_w = 8 if self.mask_xyz else 12  # floats per tangent record (gslm_tangent_views)
+        self._trec = torch.zeros(V, max(P, 1), self._trec_w, dtype=torch.float32, device=device)
         rv = self.rest_views
         self._rest_n = P * rv * (rv + 1) // 2  # floats gslm_rest_basis writes
         self._rest_R = torch.zeros((self._rest_n + 255) // 256 * 256, dtype=torch.float32,
@@ -1250,6 +1265,8 @@ class BatchedLMProblem(LMProblem, _StageTimes):
             opts.stages = STAGE_ALL | (STAGE_OVERWRITE if c0 == 0 else 0)
             opts.damp7 = self._damps if (damp and c0 == 0) else None
             opts.cg_ctl = cg_ctl
+            if not self.mask_xyz:
+                opts.flags |= MV_XYZ  # the views' head rows are the unmasked RENDER stage's
             if R is not None:
                 opts.rest_basis, opts.rest_views, opts.view_base = R.data_ptr(), self.rest_views, c0
             if dot_out is not None and c1 == V:
@@ -1269,7 +1286,12 @@ class BatchedLMProblem(LMProblem, _StageTimes):
 
     def rhs(self, out, fused=True):
         """out = J^T b in this problem's layout (xyz, exposure zeroed): per view the seeded back-to-front pass into
-        its head rows, then one gslm_gather_views -- in coordinates it writes the coordinates of J^T b directly."""
+        its head rows, then one gslm_gather_views -- in coordinates it writes the coordinates of J^T b directly.
+        mask_xyz=False: the seeded pass is a masked form, so J^T b is LMProblem's unmasked route -- gslm_backward into
+        the reference's layout, then `project`; it drops the views' row maps (tail_clean False) and the first product
+        rebuilds them."""
+        if not self.mask_xyz:
+            return LMProblem.rhs(self, out, fused=False)
         g = raw_gaussians(self.model)
         ys = self.layout.grads_struct(out)
         for b, vr in enumerate(self.views):
@@ -1317,9 +1339,9 @@ class BatchedLMProblem(LMProblem, _StageTimes):
                                                     None if opts is None else ctypes.byref(opts), self.stream),
                       "gslm_tangent_views_active")
                 continue
-            check(lib.gslm_tangent_views(vptr, c1 - c0, ctypes.byref(g), ctypes.byref(vs), 1,
+            check(lib.gslm_tangent_views(vptr, c1 - c0, ctypes.byref(g), ctypes.byref(vs), int(self.mask_xyz),
                                          self._flags.data_ptr() + 4 * c0 * P, P,
-                                         self._trec.data_ptr() + 32 * c0 * P, P,
+                                         self._trec.data_ptr() + 4 * self._trec_w * c0 * P, P,
                                          None if opts is None else ctypes.byref(opts), self.stream),
                   "gslm_tangent_views")
         self._mark(1)
@@ -1327,7 +1349,8 @@ class BatchedLMProblem(LMProblem, _StageTimes):
         for b, vr in enumerate(self.views):
             opts = self._opts(vr, 2, cg_ctl)  # RENDER
             opts.trec_in = self._trec[b].data_ptr()
-            vr.product(g, vs, self.weights[b].data_ptr(), 1, vs, opts, self.stream, "gslm_matvec_view_ex")
+            vr.product(g, vs, self.weights[b].data_ptr(), int(self.mask_xyz), vs, opts, self.stream,
+                       "gslm_matvec_view_ex")
             vr.tail_clean = True
         self._mark(2)
         # 3. every view's row sums and chain per Gaussian, y written once per chunk
@@ -1335,6 +1358,19 @@ class BatchedLMProblem(LMProblem, _StageTimes):
         self._mark(3)
         self._exposure_tail(v, y, damp, exposure_zero)
         return y
+
+
+class BatchedXyzLMProblem(BatchedLMProblem):
+    """BatchedLMProblem with the positions free: xyz is a group of unknowns like the others (the reference keeps
+    xyz_damp = 5e2 in GaussianModelDampMatrix for it).  Same passes per product -- one gslm_tangent_views, V tile
+    passes, one gslm_gather_views -- in their unmasked forms (see BatchedLMProblem); the SH-rest coordinates apply
+    unchanged.  mask_xyz must be False; union_active=True, robust, depth_weight, Marquardt damping and SSIM raise
+    ValueError, and diagonal() / cgls_jacobi refuse the problem, as they refuse LMProblem(mask_xyz=False)."""
+
+    XYZ_FREE = True
+
+    def __init__(self, model, cams, bg, gts=None, alpha_masks=None, mask_xyz=False, **kw):
+        super().__init__(model, cams, bg, gts=gts, alpha_masks=alpha_masks, mask_xyz=mask_xyz, **kw)
 
 
 class NonFiniteError(AssertionError):
@@ -2416,7 +2452,10 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     multiview: "loop" (LMProblem: the whole fused product once per training view) or "batched" (BatchedLMProblem: one
     tangent pass and one gather over the Gaussians for all the views, the SH-rest group in the views' coordinates;
     single process, recursion="fused", mask_xyz=True -- anything else raises ValueError; with one training view the
-    existing path runs).  The step comes back in the reference's layout either way.
+    existing path runs) or "batched_xyz" (BatchedXyzLMProblem: the same batch with the positions free; single process,
+    recursion="fused" and mask_xyz=False, which must be passed -- anything else raises ValueError; the rest is what the
+    loop's mask_xyz=False step does: the line search in the exact order and update_params with the xyz group).  The
+    step comes back in the reference's layout in every case.
     union_active: multiview="batched" only (else ValueError): the batched solve runs on the Gaussians at least one
     training view can move (BatchedLMProblem(union_active=True)); off by default.
     train_exposure: the step also moves the exposure rows of the training cameras (LMProblem(train_exposure=True)),
@@ -2457,14 +2496,20 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
     rank, n = world()
     sharded = collectives_on(n)
     problem_cls, evaluator_cls, solver = backend if backend is not None else (LMProblem, LossEvaluator, cgls_fused)
-    if multiview not in ("loop", "batched"):
-        raise ValueError(f"multiview must be 'loop' or 'batched', got {multiview!r}")
+    if multiview not in ("loop", "batched", "batched_xyz"):
+        raise ValueError(f"multiview must be 'loop', 'batched' or 'batched_xyz', got {multiview!r}")
     if multiview == "batched":
         if sharded or backend is not None or recursion != "fused" or not mask_xyz:
             raise ValueError("multiview='batched' is the single-process HIP problem with recursion='fused' and "
-                             "mask_xyz=True")
+                             "mask_xyz=True (multiview='batched_xyz' is the batch with the positions free)")
         if len(cams) > 1:
             problem_cls = BatchedLMProblem
+    elif multiview == "batched_xyz":
+        if sharded or backend is not None or recursion != "fused" or mask_xyz or union_active:
+            raise ValueError("multiview='batched_xyz' is the single-process HIP problem with recursion='fused' and "
+                             "mask_xyz=False, without union_active (the list's kernels are masked forms)")
+        if len(cams) > 1:
+            problem_cls = BatchedXyzLMProblem
     elif union_active:
         raise ValueError("union_active=True is an option of multiview='batched'")
     if train_exposure and (sharded or multiview != "loop" or recursion != "fused" or not mask_xyz):
@@ -2478,7 +2523,7 @@ def lm_step(model, cams, val_cams, bg, max_iter=2, restart_iter=1, damp=None, ma
         raise ValueError(f"precond must be None or 'jacobi', got {precond!r}")
     if precond == "jacobi":
         if (sharded or backend is not None or recursion != "fused" or not mask_xyz or train_exposure or
-                multiview == "batched"):
+                multiview != "loop"):
             raise ValueError("precond='jacobi' is the single-process step with multiview='loop', recursion='fused', "
                              "mask_xyz=True and no trained exposure")
         solver = cgls_jacobi

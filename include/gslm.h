@@ -558,8 +558,17 @@ int gslm_gather_screen(const gslm_view* views, int32_t nviews, const gslm_gaussi
  * product, the pixel_seed pass or the trec_in form), addressed through that view's LM row map -- so ws[b] must be
  * the geometry and scratch of a view for which GSLM_MV_TAIL_CLEAN may be passed -- and writes
  *   y = [y +] [D v +] sum_b C_b^T (sum of the head rows of Gaussian i in view b)   (views summed in index order)
- * in one pass over the Gaussians: V row sums, V chains, one read and one write of y.  xyz-masked form only: no view
- * adds to y.xyz (with OVERWRITE it is written as the D v term alone, as gslm_gather_screen does).  opts as gslm_gather_screen: the OVERWRITE bit of stages,
+ * in one pass over the Gaussians: V row sums, V chains, one read and one write of y.  Without GSLM_MV_XYZ it is the
+ * xyz-masked form: no view adds to y.xyz (with OVERWRITE it is written as the D v term alone, as gslm_gather_screen
+ * does).  GSLM_MV_XYZ in opts->flags (this entry point only): the xyz rows are part of the product.  Every
+ * ws[b].scratch must then hold 48-byte head rows, that is the rows an unmasked RENDER stage of that view (mask_xyz = 0,
+ * with or without trec_in) wrote on its current row map -- the kernel cannot check this; the scratch holds
+ * room for num_rendered 48-byte rows either way, so a mismatched call reads in bounds and computes nonsense.  The chain then
+ * includes the means (with the SH colour's view-direction term, which reads the primal SH coefficients), y.xyz is
+ * written like the other groups, the xyz groups of v and y must not be NULL, and <v, y> includes them.
+ * GSLM_ERR_INVALID with GSLM_MV_XYZ on any other entry point (gslm_matvec_view_ex / gslm_matvec_view_active have their
+ * mask_xyz argument; gslm_gather_screen, gslm_gather_views_active and gslm_tangent_views[_active] have no such form),
+ * or together with GSLM_MV_DAMP_VEC, GSLM_MV_DEPTH or GSLM_MV_EXPOSURE.  opts as gslm_gather_screen: the OVERWRITE bit of stages,
  * damp7, dot_vy / dot_scratch, cg_ctl (a stopped solve leaves y and *dot_vy as they are) and rest_basis / rest_views / view_base (y's SH-rest group then holds the
  * gslm_rest_basis coordinates).  A view with num_rendered == 0 contributes nothing and its workspaces are not
  * read (no row map exists for it).  nviews 1..16 per call (accumulate further calls).  GSLM_ERR_INVALID: NULL
@@ -572,6 +581,7 @@ typedef struct gslm_view_ws {
   size_t scratch_bytes;
   int64_t num_rendered;
 } gslm_view_ws;
+#define GSLM_MV_XYZ (1 << 6) /* 64: the next bit after GSLM_MV_DEPTH */
 int gslm_gather_views(const gslm_view* views, const gslm_view_ws* ws, int32_t nviews, const gslm_gaussians* g,
                       const gslm_grads* v, const gslm_grads* y, const gslm_matvec_opts* opts, void* stream);
 

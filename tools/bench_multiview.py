@@ -9,6 +9,7 @@ problem -- by default 1M Gaussians, SH 3, 5 x 1080p views -- through
   batched  gslm.lm.BatchedLMProblem: gslm_tangent_views, V tile passes, gslm_gather_views;
   batched_active  BatchedLMProblem(union_active=True): the same solve on the Gaussians at least one view can move
            (DESIGN.md §4.5c); also emits Pa and P, and the one-off costs of the list, the pack and the unpack.
+  loop_xyz, batched_xyz  `loop` and `batched` with the positions free (mask_xyz=False): the solve moves xyz too.
 Every run times the requested modes one after the other in one process (HIP events around a whole solve, the device
 synchronised at its end), after untimed solves of every mode that keep the GPU busy for >= 200 ms each (the clock
 settle of bench.py).  One JSON line per (run, mode) and one per mode's stage times goes to stdout and, with --out, to
@@ -93,14 +94,14 @@ def main():
 
     probs = {}
     for m in modes:
-        if m == "loop":
-            p = LMProblem(model, cams, bg, device=dev, sh_projection=False)
+        if m in ("loop", "loop_xyz"):
+            p = LMProblem(model, cams, bg, device=dev, sh_projection=False, mask_xyz=(m == "loop"))
         elif m == "gshard":
             from gslm.parallel import GaussianShardedOperator
             p = GaussianShardedOperator(LMProblem(model, cams, bg, device=dev, sh_projection=False), all_cams=cams)
-        elif m == "batched":
-            from gslm.lm import BatchedLMProblem
-            p = BatchedLMProblem(model, cams, bg, device=dev)
+        elif m in ("batched", "batched_xyz"):
+            from gslm import lm
+            p = (lm.BatchedLMProblem if m == "batched" else lm.BatchedXyzLMProblem)(model, cams, bg, device=dev)
         elif m == "batched_active":
             from gslm.lm import BatchedLMProblem
             p = BatchedLMProblem(model, cams, bg, device=dev, union_active=True)
@@ -152,15 +153,18 @@ def main():
             xs[m] = x
             emit({"kind": "cg", "run": r, "mode": m, "ms_per_iter": e0.elapsed_time(e1) / args.iters})
 
-    # the solves agree (each against the first mode, in the reference's layout)
+    # the solves agree (each against the first mode that solves the same problem -- xyz masked or free -- in the
+    # reference's layout)
     def full(m):
         p = probs[m][0]
         return p.gather_full(xs[m]) if getattr(p, "exchange", None) == "gaussian" else p.expand(xs[m])
 
-    ref = full(modes[0])
-    for m in modes[1:]:
-        emit({"kind": "agreement", "mode": m, "against": modes[0],
-              "rel_norm": float((full(m) - ref).norm() / ref.norm())})
+    firsts = {}
+    for m in modes:
+        m0 = firsts.setdefault(m.endswith("_xyz"), m)
+        if m0 != m:
+            ref = full(m0)
+            emit({"kind": "agreement", "mode": m, "against": m0, "rel_norm": float((full(m) - ref).norm() / ref.norm())})
 
     def timed(fn, reps):
         fn()
